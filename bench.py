@@ -6,6 +6,8 @@ synthetic ROI feature pairs per GPU.  Headline workload = BASELINE.json's metric
 112x112 ROI, 48 disparities -> cost volume [64,12,28,28] per ROI, entered at the feature boundary.
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full      (plus everything beyond the headline: see below)
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
   python bench.py --gpus N ...        (no WORLD_SIZE in the env: re-launches itself under torch.distributed.run, one rank per GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -13,6 +15,11 @@ Prints ONE JSON line on rank 0.  ROIs are independent units: they are sharded ac
 collective (weak scaling: fixed ROIs per GPU); a barrier + max-over-ranks brackets the timed region.  For world > 1 the
 only collective-bearing extra (the train step: one flat gradient all-reduce) runs on EVERY rank; the rank-0-only extras
 contain no collective.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the outputs of the last timed step if
+--dump-outputs is given, the line.  --full adds the rest: the sustained loop, the roofline of the dominant kernel and the per-kernel
+table, batch sensitivity, the extras (materialised cost volume, Config B, stress shapes, KITTI pair, 2D stage, train step, sharded
+inference, post-processing) and the CPU baseline; --no-cpu, --no-extra and --sustain-seconds trim a --full run.
 """
 import argparse
 import json
@@ -104,6 +111,24 @@ def max_over_ranks(elapsed, world, dev):
     return elapsed
 
 
+DUMP_LIMIT_BYTES = 64 << 20           # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(path, disparity):
+    """--dump-outputs DIR: what the timed path returned in its last timed step -- the disparity maps [N,112,112] of
+    forward_from_features, float32 -- as DIR/disparity.npy.  When that exceeds DUMP_LIMIT_BYTES, a fixed seeded sample of whole ROIs is
+    written instead (ascending ROI order), with their indices as float64 in DIR/disparity_roi_index.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    d = disparity.detach().float().cpu().numpy()
+    if d.nbytes > DUMP_LIMIT_BYTES:
+        k = DUMP_LIMIT_BYTES // (d[0].nbytes + 8)
+        idx = np.sort(np.random.default_rng(0).choice(len(d), size=k, replace=False))
+        d = d[idx]
+        np.save(os.path.join(path, "disparity_roi_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "disparity.npy"), np.ascontiguousarray(d))
+
+
 DTYPE = ("f32 (every convolution of the regressor, the three 32->1 heads included: split-f16 -- each fp32 value carried as hi + lo fp16, 3 f16-MFMA "
          "products per fp32 product, f32 accumulate; fp32-class error, tests/test_hip_s16.py.  Head gather and soft-argmin: f32 VALU)")
 
@@ -180,17 +205,19 @@ def dry_run_cpu(args, world, rank):
         dist.barrier()
     _, elapsed = timed_steps(lambda: time.sleep(0.002 * (rank + 1)), args.steps, args.warmup, world, lambda: None)
     elapsed = max_over_ranks(elapsed, world, dev)
-    # the one collective-bearing extra (train step) is entered by every rank
-    w = torch.nn.Parameter(torch.zeros(1000))
-    w.grad = torch.full((1000,), float(rank + 1))
-    sync = GradientSync([w])
-    t0 = time.perf_counter()
-    sync()
-    allreduce_ms = (time.perf_counter() - t0) * 1e3
-    ok = bool(torch.allclose(w.grad, torch.full((1000,), (world + 1) / 2.0)))
+    extra = {"dry_run_cpu": True}
+    if args.full:
+        # the one collective-bearing extra (train step) is entered by every rank
+        w = torch.nn.Parameter(torch.zeros(1000))
+        w.grad = torch.full((1000,), float(rank + 1))
+        sync = GradientSync([w])
+        t0 = time.perf_counter()
+        sync()
+        allreduce_ms = (time.perf_counter() - t0) * 1e3
+        extra["grad_sync_ok"] = bool(torch.allclose(w.grad, torch.full((1000,), (world + 1) / 2.0)))
+        extra["grad_allreduce_ms"] = round(allreduce_ms, 3)
     if rank == 0:
-        line = headline(args.rois * args.steps * world, elapsed, args, world, args.rois, None, None,
-                        {"dry_run_cpu": True, "grad_sync_ok": ok, "grad_allreduce_ms": round(allreduce_ms, 3)})
+        line = headline(args.rois * args.steps * world, elapsed, args, world, args.rois, None, None, extra)
         line["data"] = "none (dry run of the control flow on CPU/gloo: no kernels executed, value is not a measurement)"
         print(json.dumps(line), flush=True)
     if world > 1:
@@ -204,9 +231,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rois", type=int, default=DEFAULT_ROIS, help="ROI pairs per step per GPU")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--sustain-seconds", type=float, default=10.0, help="rank 0, one GPU: loop the headline step this long for extra.sustained (0: skip)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra measurements (Config B, stress, KITTI pair, train step, post-processing)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: sustained loop, roofline, batch sensitivity, extras, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (rank 0) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--sustain-seconds", type=float, default=10.0, help="--full, rank 0, one GPU: loop the headline step this long for extra.sustained (0: skip)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra measurements (Config B, stress, KITTI pair, train step, post-processing)")
     ap.add_argument("--dry-run-cpu", action="store_true", help=argparse.SUPPRESS)   # tests/test_bench_flow.py: control flow on gloo, no kernels
     args = ap.parse_args()
 
@@ -253,11 +283,14 @@ def main():
         out, elapsed = timed_steps(step, args.steps, args.warmup, world, torch.cuda.synchronize)
     assert torch.isfinite(out).all()
     elapsed = max_over_ranks(elapsed, world, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
-    # ---- the same step held for >= 10 s (rank 0, one GPU): does the K-step rate survive power / thermal steady state?
+    # ---- everything below runs with --full only.
+    # The same step held for >= 10 s (rank 0, one GPU): does the K-step rate survive power / thermal steady state?
     extra = {}
     value_override = None
-    if rank == 0 and world == 1 and args.sustain_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.sustain_seconds > 0:
         with torch.no_grad():
             sus = sustained_run(step, N, args.sustain_seconds, N * args.steps / elapsed)
         extra["sustained"] = sus
@@ -266,7 +299,7 @@ def main():
 
     # ---- roofline of the dominant kernel: per-launch HIP events on the launch stream, same K steps, same inputs
     roofline = None
-    if rank == 0:
+    if args.full and rank == 0:
         E.TIMING = []
         with torch.no_grad():
             for _ in range(args.steps):
@@ -349,9 +382,9 @@ def main():
 
     # ---- extras.  The train step is the only one with a collective (one flat gradient all-reduce): EVERY rank enters it.
     # The others have none and run on rank 0 at world size 1 only (the scaling runs stay short; their numbers do not depend on N).
-    if rank == 0:
+    if args.full and rank == 0:
         extra["world"] = world_info(dev, world)
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         try:
             tr = train_step_extra(dev, model, world)
             if rank == 0:
@@ -373,7 +406,7 @@ def main():
             extra["skipped_for_world_gt_1"] = ["config_b_full_psmnet", "stress_64roi_224x224x96", "kitti_pair_r50fpn_plus_16roi", "post_process_16img_x16roi"]
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline_config_a(sd)
 
     if rank == 0:

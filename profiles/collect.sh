@@ -9,7 +9,7 @@ TAG=${1:-r2}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_$TAG
 mkdir -p "$OUT"
-BENCH="python bench.py --steps 10 --warmup 3 --no-cpu --no-extra"
+BENCH="python bench.py --steps 10 --warmup 3 --full --no-cpu --no-extra"
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o trace -- $BENCH > "$OUT/trace.log" 2>&1
 timeout 400 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d "$OUT" -o fetch -- $BENCH > "$OUT/fetch.log" 2>&1
 timeout 400 rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -d "$OUT" -o write -- $BENCH > "$OUT/write.log" 2>&1

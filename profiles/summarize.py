@@ -41,7 +41,7 @@ def main(out, tag):
         for r in csv.DictReader(open(tr[0])):
             rows[short(r["Kernel_Name"])].append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
     tot = sum(sum(v) for v in rows.values()) or 1
-    cmd = os.environ.get("PROF_CMD", "python bench.py --steps 10 --warmup 3 --no-cpu --no-extra` (plus the instrumented repeat of the same 10 steps)")
+    cmd = os.environ.get("PROF_CMD", "python bench.py --steps 10 --warmup 3 --full --no-cpu --no-extra` (plus the instrumented repeat of the same 10 steps)")
     commit = os.environ.get("PROF_COMMIT", "unknown")
     lines = [f"# rocprofv3 --kernel-trace --stats summary ({tag})", "", f"Commit: `{commit}`", "", f"Command: `{cmd}`" if not cmd.endswith(")") else f"Command: `{cmd}", ""]
     bl = os.path.join(out, "bench_line.json")

@@ -1,4 +1,5 @@
-"""Pins oracle/nms_oracle.py to the reference's own nms_cpu (tests/golden/nms_golden.npz; live binary when oracle/_ref is built)."""
+"""Pins oracle/nms_oracle.py to the reference's own nms_cpu (tests/golden/nms_golden.npz, ref_live_golden.npz; live binary when
+oracle/_ref is built)."""
 import os
 
 import numpy as np
@@ -6,6 +7,7 @@ import pytest
 import torch
 
 from oracle import nms_oracle as N
+from tests.golden import make_golden_ref_live as LIVE
 from tests.golden.make_golden_nms import CASES, proposals
 
 G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "nms_golden.npz"), allow_pickle=False)
@@ -23,13 +25,13 @@ def test_oracle_edge_cases_and_live_binary():
     d = np.array([[10, 10, 50, 50]] * 3, dtype=np.float32)
     s = np.array([0.3, 0.9, 0.5], dtype=np.float32)
     assert N.nms(d, s, 0.5).tolist() == [1] and N.nms(d, s, 1.0).tolist() == [1] and N.nms(d, s, 1.0, strict=True).tolist() == [0, 1, 2]
+    # random boxes: the reference kernel's kept indices recorded in tests/golden/ref_live_golden.npz, and the live module when built
     from oracle import build_ref
     ref = build_ref.load()
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
-    g = torch.Generator().manual_seed(3)
-    for n, thr in ((300, 0.6), (77, 0.2)):
-        xy = torch.rand(n, 2, generator=g) * 200
-        wh = torch.rand(n, 2, generator=g) * 80 + 1
-        dets, scores = torch.cat([xy, xy + wh], 1), torch.rand(n, generator=g)
-        assert np.array_equal(N.nms(dets.numpy(), scores.numpy(), thr), ref.nms(dets, scores, thr).numpy())
+    z = LIVE.load()
+    for n, thr in LIVE.NMS_CASES:
+        dets, scores = z[f"nms_{n}_dets"], z[f"nms_{n}_scores"]
+        got = N.nms(dets, scores, thr)
+        assert np.array_equal(got, z[f"nms_{n}_keep"]), n
+        if ref is not None:
+            assert np.array_equal(got, ref.nms(torch.from_numpy(dets), torch.from_numpy(scores), thr).numpy()), n

@@ -91,19 +91,17 @@ def test_oracle_matches_reference_kernel_caller_crops_bit_exact():
 
 
 def test_oracle_matches_reference_binary_live_when_present():
-    """When oracle/_ref holds the compiled reference kernel (authoring container, or shipped with the snapshot), random rois
-    are checked live and bit for bit, beyond what the fixture stores."""
-    import pytest
+    """Random rois (partly outside, some malformed) on a random image, bit for bit against the reference kernel's outputs recorded
+    in tests/golden/ref_live_golden.npz, and against the live module when oracle/_ref holds the compiled reference kernel."""
     import torch
     from oracle import build_ref
+    from tests.golden import make_golden_ref_live as LIVE
     ref = build_ref.load()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (python oracle/build_ref.py needs /root/reference)")
-    g = torch.Generator().manual_seed(7)
-    img = torch.rand(3, 2, 61, 83, generator=g)
-    xy = torch.rand(40, 2, generator=g) * torch.tensor([90.0, 70.0]) - 5
-    wh = torch.rand(40, 2, generator=g) * torch.tensor([70.0, 60.0]) - 2
-    rois = torch.cat([torch.randint(0, 3, (40, 1), generator=g).float(), xy, xy + wh], 1)
-    for ph, pw, sr, scale in [(7, 7, 0, 1.0), (5, 9, 2, 0.5), (16, 16, 0, 1.0)]:
-        want = ref.roi_align_forward(img, rois, scale, ph, pw, sr).numpy()
-        assert np.array_equal(R.roi_align(img.numpy(), rois.numpy(), scale, ph, pw, sr), want)
+    z = LIVE.load()
+    img, rois = z["roi_img"], z["roi_rois"]
+    for k, (ph, pw, sr, scale) in enumerate(LIVE.ROI_SETTINGS):
+        got = R.roi_align(img, rois, scale, ph, pw, sr)
+        assert np.array_equal(got, z[f"roi_out{k}"]), (ph, pw, sr, scale)
+        if ref is not None:
+            want = ref.roi_align_forward(torch.from_numpy(img), torch.from_numpy(rois), scale, ph, pw, sr).numpy()
+            assert np.array_equal(got, want), (ph, pw, sr, scale)
