@@ -1,0 +1,58 @@
+"""ctypes binding of libdisprcnn_pts.so (the C ABI declared in include/disprcnn_pts.h).
+
+As disprcnn_amd/_lib.py: NO fallback -- if the library is missing or a symbol is absent, ``lib()`` raises, and a non-zero
+status becomes ``RuntimeError``.
+"""
+import ctypes as C
+import os
+
+import torch  # noqa: F401  -- must be imported BEFORE the .so: both must share torch's libamdhip64 runtime
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libdisprcnn_pts.so")
+
+_P = C.c_void_p
+_I = C.c_int
+_L = C.c_int64
+_F = C.c_float
+_SIGS = {
+    "drc_pts_version": (C.c_char_p, []),
+    "drc_instance_points_fwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _F, _I, _P, _P, _L, _P]),
+    "drc_instance_points_gather_fwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P]),
+    "drc_pn2_furthest_point_sampling": (_I, [_I, _I, _I, _P, _P, _P, _I, _P]),
+    "drc_pn2_gather_points": (_I, [_I, _I, _I, _I, _P, _P, _P, _P]),
+    "drc_pn2_ball_query": (_I, [_I, _I, _I, _F, _I, _P, _P, _P, _P]),
+    "drc_pn2_group_points": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "drc_pn2_three_nn": (_I, [_I, _I, _I, _P, _P, _P, _P, _P]),
+    "drc_pn2_three_interpolate": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "drc_pn2_csr_bounds": (_I, [_I, _I, _I, _P, _P, _P, _P]),
+    "drc_pn2_csr_scatter_add": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+}
+
+EXPORTED_SYMBOLS = tuple(_SIGS)
+
+_lib = None
+
+
+def lib():
+    """Load (once) and return the point-ops library; raise loudly if it is not built."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError(
+                f"{LIB_PATH} is missing: the point-ops HIP library is not built. Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (or python -m disprcnn_amd.pts.build). "
+                "There is no CPU/torch fallback for this path.")
+        handle = C.CDLL(LIB_PATH)
+        for name, (res, args) in _SIGS.items():
+            fn = getattr(handle, name)  # AttributeError if the symbol is not exported
+            fn.restype = res
+            fn.argtypes = args
+        _lib = handle
+    return _lib
+
+
+def check(status, what):
+    if status != 0:
+        kind = "bad argument / unsupported shape" if status < 0 else "hipError_t"
+        raise RuntimeError(f"{what} failed: status {status} ({kind})")
