@@ -9,13 +9,15 @@ def opt_n_threads(n):
     return max(min(1 << int(math.log(float(n)) / math.log(2.0)), 1024), 1)
 
 
-def fps(xyz, m):
-    """sampling_gpu.cu: per-slot running best (strict >), then the shared-memory tree (ties keep the lower slot of each pair)."""
+def fps(xyz, m, return_temp=False):
+    """sampling_gpu.cu: per-slot running best (strict >), then the shared-memory tree (ties keep the lower slot of each pair).
+    return_temp: also return the final `temp` [B,N] the kernel leaves behind, the running minimum distance (1e10 where m <= 1)."""
     xyz = np.asarray(xyz, np.float32)
     B, N, _ = xyz.shape
     bs = opt_n_threads(N)
     rows = -(-N // bs)
     out = np.zeros((B, m), np.int32)
+    temps = np.full((B, N), 1e10, np.float32)
     for b in range(B):
         p = xyz[b]
         temp = np.full(N, 1e10, np.float32)
@@ -37,7 +39,8 @@ def fps(xyz, m):
                 s //= 2
             old = int(idx[0])
             out[b, j] = old
-    return out
+        temps[b] = temp
+    return (out, temps) if return_temp else out
 
 
 def ball_query(radius, nsample, xyz, new_xyz):
@@ -80,9 +83,15 @@ def three_nn(unknown, known):
     return dist2, idx
 
 
+def _take(p, idx):
+    """p[:, idx] with the API's rule for an index outside [0, N): it reads 0 (pointnet2.hip; the reference has no check)."""
+    ok = (idx >= 0) & (idx < p.shape[1])
+    return np.where(ok, p[:, np.where(ok, idx, 0)], np.float32(0))
+
+
 def gather(points, idx):
     points, idx = np.asarray(points, np.float32), np.asarray(idx)
-    return np.stack([points[b][:, idx[b]] for b in range(points.shape[0])])
+    return np.stack([_take(points[b], idx[b]) for b in range(points.shape[0])])
 
 
 def group(points, idx):
@@ -94,12 +103,13 @@ def three_interpolate(points, idx, weight):
     out = []
     for b in range(points.shape[0]):
         p = points[b]
-        out.append(weight[b, :, 0] * p[:, idx[b, :, 0]] + weight[b, :, 1] * p[:, idx[b, :, 1]] + weight[b, :, 2] * p[:, idx[b, :, 2]])
+        out.append(weight[b, :, 0] * _take(p, idx[b, :, 0]) + weight[b, :, 1] * _take(p, idx[b, :, 1]) + weight[b, :, 2] * _take(p, idx[b, :, 2]))
     return np.stack(out)
 
 
 def scatter_grad(grad_out, idx, n, weight=None):
-    """float64 reference of the three backward ops: grad_out [B,C,K], idx [B,E] (E = K, or 3K with weight [B,E])."""
+    """float64 reference of the three backward ops: grad_out [B,C,K], idx [B,E] (E = K, or 3K with weight [B,E]).
+    An index outside [0, n) contributes nothing."""
     grad_out, idx = np.asarray(grad_out, np.float64), np.asarray(idx).reshape(grad_out.shape[0], -1)
     B, C, K = grad_out.shape
     per = idx.shape[1] // K
@@ -109,5 +119,6 @@ def scatter_grad(grad_out, idx, n, weight=None):
         v = grad_out[b][:, cols]
         if weight is not None:
             v = v * np.asarray(weight, np.float64).reshape(B, -1)[b][None]
-        np.add.at(out[b].T, idx[b], v.T)
+        ok = (idx[b] >= 0) & (idx[b] < n)
+        np.add.at(out[b].T, idx[b][ok], v.T[ok])
     return out

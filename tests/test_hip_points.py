@@ -19,13 +19,17 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _golden_inputs(dev, g=None):
+EDGES = os.path.join(os.path.dirname(__file__), "golden", "points_ref_edges_golden.npz")
+
+
+def _golden_inputs(dev, g=None, cams=None):
+    """Per-image BoxLists and Calibs of a golden scene.  cams: one (P2, P3) per image; by default the two cameras of GOLDEN."""
     from disprcnn_amd.structures.bounding_box import BoxList
     from disprcnn_amd.structures.calib import Calib
     g = g if g is not None else np.load(GOLDEN)
     W, H = int(g["W"]), int(g["H"])
     left, right, calibs, r = [], [], [], 0
-    cams = [(g["P2"], g["P3"]), (g["P2B"], g["P3B"])]
+    cams = cams if cams is not None else [(g["P2"], g["P3"]), (g["P2B"], g["P3B"])]
     for i, n in enumerate(g["rois_per_image"].tolist()):
         lb = BoxList(torch.from_numpy(g["left_boxes"][r:r + n]).to(dev), (W, H))
         lb.add_field("disparity", torch.from_numpy(g["disparity"][r:r + n]).to(dev))
@@ -37,11 +41,12 @@ def _golden_inputs(dev, g=None):
     return left, right, calibs
 
 
-def test_instance_points_match_the_reference(dev):
-    from disprcnn_amd.modeling.pointcloud import InstancePointCloud
-    g = np.load(GOLDEN)
-    ipc = InstancePointCloud(npoints=int(g["npoints"]))
-    pts, mean, rot = ipc(*_golden_inputs(dev, g))
+def _edge_cams(g):
+    return list(zip(g["P2s"], g["P3s"]))
+
+
+def _check_against(g, ipc, pts, mean, rot):
+    """InstancePointCloud's outputs vs a golden scene; returns the per-point scale of the bound."""
     assert pts.shape == g["pts"].shape and mean.shape == g["pts_mean"].shape and rot.dtype == torch.float64
     assert ipc.last_counts == g["counts"].tolist()
     src = ipc.last_src_pix.cpu().numpy()
@@ -58,8 +63,44 @@ def test_instance_points_match_the_reference(dev):
     assert (np.abs(mean.cpu().numpy() - g["pts_mean"]) <= 2e-4 * ms + 1e-4).all()
     # centred points: the same error bound (it comes from the depth, not from the centred magnitude)
     assert (np.abs(pts.cpu().numpy() - g["pts"]) <= 2 * (2e-4 * scale + 1e-4)).all()
+    return scale
+
+
+def test_instance_points_match_the_reference(dev):
+    from disprcnn_amd.modeling.pointcloud import InstancePointCloud
+    g = np.load(GOLDEN)
+    ipc = InstancePointCloud(npoints=int(g["npoints"]))
+    pts, mean, rot = ipc(*_golden_inputs(dev, g))
+    scale = _check_against(g, ipc, pts, mean, rot)
     back = InstancePointCloud.rotate_back(pts + mean[:, None], rot)
     assert back.shape == pts.shape and torch.isfinite(back).all()
+    # ... and it inverts the rotation: the reference's points rotated back in fp64, at the same bound
+    ref = g["pts"] + g["pts_mean"][:, None]
+    a = -g["rot_angle"][:, None]
+    ref_back = ref.astype(np.float64).copy()
+    ref_back[..., 0] = ref[..., 0] * np.cos(a) - ref[..., 2] * np.sin(a)
+    ref_back[..., 2] = ref[..., 0] * np.sin(a) + ref[..., 2] * np.cos(a)
+    assert (np.abs(back.cpu().numpy() - ref_back) <= 2e-4 * scale + 1e-4).all()
+
+
+def test_instance_points_match_the_reference_at_the_edges(dev):
+    """points_ref_edges_golden.npz (make_golden_points.py --edges): depths past the 160 m clamp, negative disparity, right boxes wider
+    and narrower than the left, boxes on all four image borders, 1-px-high and 2-px-wide boxes, a graded mask, a non-empty mask the
+    reference does not apply, an image without ROIs, and > 1<<20 box pixels in all (the workspace grows)."""
+    from disprcnn_amd.modeling.pointcloud import InstancePointCloud
+    g = np.load(EDGES)
+    assert not g["mask_applied"].all() and g["rois_per_image"][1] == 0
+    ipc = InstancePointCloud(npoints=int(g["npoints"]))
+    pts, mean, rot = ipc(*_golden_inputs(dev, g, _edge_cams(g)))
+    assert ipc._ws[dev].numel() > 1 << 20                                # the regrow pass ran
+    scale = _check_against(g, ipc, pts, mean, rot)
+    # rotate_back undoes the rotation: back_project's points (before rotation) at the same bound
+    back = InstancePointCloud.rotate_back(pts + mean[:, None], rot).cpu().numpy()
+    assert (np.abs(back - g["pts_pre_rotation"]) <= 2e-4 * scale + 1e-4).all(), np.abs(back - g["pts_pre_rotation"]).max()
+    assert (g["pts_pre_rotation"][..., 2] == 160).any()                 # the max_depth clamp acted
+    # a second, smaller call on the grown workspace
+    g0 = np.load(GOLDEN)
+    _check_against(g0, ipc, *ipc(*_golden_inputs(dev, g0)))
 
 
 def test_instance_points_are_bit_identical_across_calls(dev):

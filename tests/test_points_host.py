@@ -105,3 +105,67 @@ def test_oracle_gather_group_interpolate_and_scatter():
     i3 = np.array([[[0, 1, 1]], [[2, 2, 2]]], np.int32)
     assert O.three_interpolate(pts, i3, w)[:, 0, 0].tolist() == [0.5 * 0 + 0.5 * 1 + 0.5 * 1, 1.5 * 12]
     assert O.scatter_grad(np.ones((2, 2, 1), np.float32), i3, 5, w)[0, 0].tolist() == [0.5, 1.0, 0, 0, 0]
+
+
+# d^2 = 9 from the origin for every point but point 0: a cloud whose first FPS step ties in every slot
+_TIE9 = np.array([[[0, 0, 0], [3, 0, 0], [0, 3, 0], [0, 0, 3], [-3, 0, 0], [0, -3, 0], [0, 0, -3], [2, 2, 1], [-2, -2, -1], [2, 1, 2],
+                   [1, 2, 2], [-2, -1, -2]]], np.float32)
+
+
+def test_oracle_fps_tie_order_at_block_size_8_with_ties_in_every_slot():
+    # N = 12 -> block size 8: slot s holds points s and s + 8 (s < 4).  Step 1: every point but 0 is at d^2 = 9, so all eight slots
+    # tie; slot 0 (bit-reversed 0) wins with its first point at the maximum, point 8.  Step 2 from point 8 leaves
+    # temp = [0,9,9,9,6,6,9,9,0,9,9,2]: slots 1,2,3,6,7 tie at 9 with bit-reversed keys 4,2,6,3,7 -> slot 2, and of its points 2 and 10
+    # (both 9) the first, 2.  Lowest-slot order would give point 1, last-in-slot order point 10.
+    idx, temp = O.fps(_TIE9, 3, return_temp=True)
+    assert O.opt_n_threads(12) == 8
+    assert idx.tolist() == [[0, 8, 2]]
+    assert temp.tolist() == [[0, 9, 9, 9, 6, 6, 9, 9, 0, 9, 9, 2]]        # the last step's running minimum (from point 8)
+
+
+def test_oracle_fps_tie_order_at_block_size_4_and_m_beyond_n():
+    # N = 4 -> block size 4.  From 0: slots 1,2,3 tie at 1 -> keys 2,1,3 -> point 2.  temp [0,1,1,1] -> from 2 (0,1,0): [0,1,0,1]
+    # -> slots 1 and 3 tie -> point 1.  -> from 1: [0,0,0,1] -> point 3.  Then every distance is 0: slot 0, point 0, for ever.
+    xyz = np.array([[[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]]], np.float32)
+    idx, temp = O.fps(xyz, 7, return_temp=True)
+    assert idx.tolist() == [[0, 2, 1, 3, 0, 0, 0]]
+    assert temp.tolist() == [[0, 0, 0, 0]]
+    # m = 1: the kernel never updates temp
+    idx, temp = O.fps(xyz, 1, return_temp=True)
+    assert idx.tolist() == [[0]] and (temp == np.float32(1e10)).all()
+
+
+def test_oracle_ball_query_at_the_radius_without_hits_and_with_nsample_beyond_the_hits():
+    # 0.5-grid coordinates: every squared distance is exact.  (1,0,0), (0,-1,0) and (0,0,1) sit on the unit sphere: `d2 < r2` is
+    # strict, so they are not neighbours; points 1, 3 and 5 are (d2 0.25, 0.75, 0.5).
+    xyz = np.array([[[1, 0, 0], [0.5, 0, 0], [0, -1, 0], [0.5, 0.5, 0.5], [0, 0, 1], [-0.5, 0, 0.5]]], np.float32)
+    new = np.array([[[0, 0, 0], [10, 10, 10], [1, 0, 0]]], np.float32)
+    idx = O.ball_query(1.0, 5, xyz, new)
+    assert idx[0, 0].tolist() == [1, 3, 5, 1, 1]                 # nsample 5 > 3 hits: padded with the first hit
+    assert idx[0, 1].tolist() == [0] * 5                         # no neighbour: the row stays as the caller zeroed it
+    assert idx[0, 2].tolist() == [0, 1, 3, 0, 0]                 # (1,0,0): itself, (0.5,0,0) and (0.5,0.5,0.5) (d2 0.75); rest >= 2
+    idx = O.ball_query(1.0, 8, xyz, new[:, 2:])
+    assert idx[0, 0].tolist() == [0, 1, 3, 0, 0, 0, 0, 0]
+    assert O.ball_query(0.0, 3, xyz, xyz).tolist() == np.zeros((1, 6, 3)).tolist()   # radius 0: d2 < 0 never holds
+
+
+def test_oracle_three_nn_with_fewer_than_three_known_points_and_exact_ties():
+    u = np.array([[[0, 0, 0]]], np.float32)
+    d2, idx = O.three_nn(u, np.array([[[1, 0, 0]]], np.float32))
+    assert idx.tolist() == [[[0, 0, 0]]] and d2[0, 0, 0] == 1 and np.isinf(d2[0, 0, 1:]).all()   # (float)1e40 = inf, index 0
+    d2, idx = O.three_nn(u, np.array([[[0, 2, 0], [1, 0, 0]]], np.float32))
+    assert idx.tolist() == [[[1, 0, 0]]] and d2[0, 0, :2].tolist() == [1, 4] and np.isinf(d2[0, 0, 2])
+    # four known points at d2 = 1 (exact ties) behind a farther one: the first three in index order win
+    d2, idx = O.three_nn(u, np.array([[[2, 0, 0], [0, 1, 0], [-1, 0, 0], [0, 0, 1], [1, 0, 0]]], np.float32))
+    assert idx.tolist() == [[[1, 2, 3]]] and d2.tolist() == [[[1, 1, 1]]]
+
+
+def test_oracle_out_of_range_indices_read_zero_and_are_skipped_in_backward():
+    pts = np.arange(1, 11, dtype=np.float32).reshape(1, 2, 5)
+    idx = np.array([[-1, 5, 2147483647, 3]], np.int32)
+    assert O.gather(pts, idx).tolist() == [[[0, 0, 0, 4], [0, 0, 0, 9]]]
+    assert O.group(pts, idx.reshape(1, 2, 2)).tolist() == [[[[0, 0], [0, 4]], [[0, 0], [0, 9]]]]
+    w = np.array([[[0.5, 0.25, 2.0]]], np.float32)
+    assert O.three_interpolate(pts, np.array([[[1, -1, 4]]], np.int32), w).tolist() == [[[0.5 * 2 + 2.0 * 5], [0.5 * 7 + 2.0 * 10]]]
+    g = O.scatter_grad(np.ones((1, 2, 4), np.float32), idx, 5)
+    assert g.tolist() == [[[0, 0, 0, 1, 0], [0, 0, 0, 1, 0]]]
