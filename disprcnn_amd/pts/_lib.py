@@ -27,6 +27,12 @@ _SIGS = {
     "drc_pn2_three_interpolate": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "drc_pn2_csr_bounds": (_I, [_I, _I, _I, _P, _P, _P, _P]),
     "drc_pn2_csr_scatter_add": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "drc_box3d_bev": (_I, [_I, _I, _P, _P, _I, _P, _P]),
+    "drc_box3d_iou3d": (_I, [_I, _I, _P, _P, _P, _P]),
+    "drc_box3d_nms": (_I, [_I, _I, _P, _P, _F, _I, _I, _P, _P, _I, _P, _P]),
+    "drc_roipool3d_fwd": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "drc_box3d_max_pool_samples": (_I, []),
+    "drc_pts_in_boxes3d": (_I, [_I, _I, _I, _P, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

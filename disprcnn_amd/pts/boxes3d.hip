@@ -1,0 +1,440 @@
+// boxes3d.hip -- PointRCNN's 3D box ops (gfx950): rotated BEV overlap / IoU, fused 3D IoU, batched rotated and axis-aligned NMS,
+// roipool3d and the per-point in-box flags.
+//
+//   reference: point_rcnn/lib/utils/iou3d/src/iou3d_kernel.cu (box_overlap, iou_bev, iou_normal, nms_kernel, nms_normal_kernel),
+//              iou3d_utils.py (boxes_iou3d_gpu), roipool3d/src/roipool3d_kernel.cu (pt_in_box3d, get_pooled_idx, roipool3d_forward).
+//
+// Every value is the reference's fp32 expression, evaluated in the same order (the library builds with -ffp-contract=off).  The
+// schedules are ours:
+//   - a box's centre, rotated corners and trigonometry are computed once per box (rows: once per LDS tile, columns: once per lane),
+//     not once per pair;
+//   - the <= 24-point intersection polygon lives in registers: each candidate, in the reference's append order, lands in its
+//     compacted slot through a select over the slots it can reach, then a stable insertion sort orders it as the reference's
+//     bubble sort does; loops stop once no lane of the wave needs more.  No runtime-indexed private array, so no scratch;
+//   - NMS: one wave per 64x64 tile, the lane is the column and __ballot gives each row's 64-bit word; tiles below the diagonal
+//     (never read by the walk) are skipped.  The greedy walk runs on the device, one wave per batch row, the removal words spread
+//     over the lanes (8 per lane: n <= 32768), and stops at max_keep;
+//   - roipool3d: one workgroup per (batch, box) scans the points in index order, a ballot + popcount prefix places the first S
+//     in-box indices in LDS, then whole output rows are gathered with coalesced stores.  No B*N*M assignment buffer.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/disprcnn_pts.h"
+
+namespace {
+
+constexpr float kEps = 1e-8f;               // iou3d_kernel.cu EPS
+constexpr float kMargin = 1e-5f;            // check_in_box2d MARGIN
+constexpr int kPoly = 24;                   // 16 edge intersections + 8 corners
+constexpr int kWalkSlots = 8;               // removal words per lane in the walk
+constexpr int kMaxNmsBoxes = 64 * 64 * kWalkSlots;
+constexpr int kPoolThreads = 256;
+constexpr int kMaxPoolSamples = 8192;       // LDS index list of roipool3d: 32 KB
+constexpr float kMaxDis = 10.0f;            // roipool3dLauncher's max_dis
+
+// One box [x1, y1, x2, y2, ry], everything box_overlap / check_in_box2d / iou_bev derive from it alone.
+struct BoxG {
+    float x1, y1, x2, y2;
+    float cx, cy;                           // (x1 + x2) / 2, (y1 + y2) / 2
+    float cn, sn;                           // cos(-ry), sin(-ry): check_in_box2d
+    float px[4], py[4];                     // corners (x1,y1) (x2,y1) (x2,y2) (x1,y2) rotated about the centre by ry
+    float area;                             // (x2 - x1) * (y2 - y1): iou_bev
+};
+
+__device__ __forceinline__ BoxG box_geom(float x1, float y1, float x2, float y2, float ry) {
+    BoxG g;
+    g.x1 = x1; g.y1 = y1; g.x2 = x2; g.y2 = y2;
+    g.cx = (x1 + x2) / 2;
+    g.cy = (y1 + y2) / 2;
+    g.cn = cosf(-ry);
+    g.sn = sinf(-ry);
+    const float c = cosf(ry), s = sinf(ry);
+    const float xs[4] = {x1, x2, x2, x1}, ys[4] = {y1, y1, y2, y2};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {           // rotate_around_center
+        g.px[k] = (xs[k] - g.cx) * c + (ys[k] - g.cy) * s + g.cx;
+        g.py[k] = -(xs[k] - g.cx) * s + (ys[k] - g.cy) * c + g.cy;
+    }
+    g.area = (x2 - x1) * (y2 - y1);
+    return g;
+}
+
+__device__ __forceinline__ BoxG box_geom5(const float* b) { return box_geom(b[0], b[1], b[2], b[3], b[4]); }
+
+// kitti_utils.boxes3d_to_bev_torch of one [x, y, z, h, w, l, ry] box
+__device__ __forceinline__ BoxG box_geom7(const float* b) {
+    const float half_l = b[5] / 2, half_w = b[4] / 2;
+    return box_geom(b[0] - half_l, b[2] - half_w, b[0] + half_l, b[2] + half_w, b[6]);
+}
+
+__device__ __forceinline__ bool in_box2d(const BoxG& g, float x, float y) {      // check_in_box2d
+    const float rx = (x - g.cx) * g.cn + (y - g.cy) * g.sn + g.cx;
+    const float ry = -(x - g.cx) * g.sn + (y - g.cy) * g.cn + g.cy;
+    return rx > g.x1 - kMargin && rx < g.x2 + kMargin && ry > g.y1 - kMargin && ry < g.y2 + kMargin;
+}
+
+__device__ __forceinline__ float cross3(float p1x, float p1y, float p2x, float p2y, float p0x, float p0y) {
+    return (p1x - p0x) * (p2y - p0y) - (p2x - p0x) * (p1y - p0y);
+}
+
+// intersection(p1, p0, q1, q0, ans): segment p0-p1 against q0-q1
+__device__ __forceinline__ bool intersection(float p1x, float p1y, float p0x, float p0y, float q1x, float q1y, float q0x, float q0y,
+                                             float& ax, float& ay) {
+    const bool rect = fminf(p0x, p1x) <= fmaxf(q0x, q1x) && fminf(q0x, q1x) <= fmaxf(p0x, p1x) &&
+                      fminf(p0y, p1y) <= fmaxf(q0y, q1y) && fminf(q0y, q1y) <= fmaxf(p0y, p1y);
+    if (!rect) return false;
+    const float s1 = cross3(q0x, q0y, p1x, p1y, p0x, p0y);
+    const float s2 = cross3(p1x, p1y, q1x, q1y, p0x, p0y);
+    const float s3 = cross3(p0x, p0y, q1x, q1y, q0x, q0y);
+    const float s4 = cross3(q1x, q1y, p1x, p1y, q0x, q0y);
+    if (!(s1 * s2 > 0 && s3 * s4 > 0)) return false;
+    const float s5 = cross3(q1x, q1y, p1x, p1y, p0x, p0y);
+    if (fabsf(s5 - s1) > kEps) {
+        ax = (s5 * q0x - s1 * q1x) / (s5 - s1);
+        ay = (s5 * q0y - s1 * q1y) / (s5 - s1);
+    } else {
+        const float a0 = p0y - p1y, b0 = p1x - p0x, c0 = p0x * p1y - p1x * p0y;
+        const float a1 = q0y - q1y, b1 = q1x - q0x, c1 = q0x * q1y - q1x * q0y;
+        const float D = a0 * b1 - a1 * b0;
+        ax = (b0 * c1 - b1 * c0) / D;
+        ay = (a1 * c0 - a0 * c1) / D;
+    }
+    return true;
+}
+
+// Append candidate (x, y) to cross_points[cnt] when ok: a select over the compile-time slots d <= s it can land in.
+template <int s>
+__device__ __forceinline__ void poly_append(bool ok, float x, float y, int& cnt, float& sx, float& sy, float (&qx)[kPoly], float (&qy)[kPoly]) {
+#pragma unroll
+    for (int d = 0; d <= s; ++d)
+        if (ok && cnt == d) { qx[d] = x; qy[d] = y; }
+    if (ok) { sx = sx + x; sy = sy + y; ++cnt; }
+}
+
+template <int i, int j>
+__device__ __forceinline__ void poly_edge(const BoxG& A, const BoxG& B, int& cnt, float& sx, float& sy, float (&qx)[kPoly], float (&qy)[kPoly]) {
+    constexpr int i1 = (i + 1) & 3, j1 = (j + 1) & 3;
+    float x = 0.f, y = 0.f;
+    const bool ok = intersection(A.px[i1], A.py[i1], A.px[i], A.py[i], B.px[j1], B.py[j1], B.px[j], B.py[j], x, y);
+    poly_append<i * 4 + j>(ok, x, y, cnt, sx, sy, qx, qy);
+}
+
+// box_overlap(a, b).  Uses wave votes to cut its loops short: every lane of the wave must call it (inactive lanes are fine).
+__device__ __forceinline__ float box_overlap(const BoxG& A, const BoxG& B) {
+    float qx[kPoly], qy[kPoly], qk[kPoly];
+#pragma unroll
+    for (int d = 0; d < kPoly; ++d) { qx[d] = 0.f; qy[d] = 0.f; qk[d] = 0.f; }
+    float sx = 0.f, sy = 0.f;               // poly_center: the sum in append order, then / cnt
+    int cnt = 0;
+    poly_edge<0, 0>(A, B, cnt, sx, sy, qx, qy); poly_edge<0, 1>(A, B, cnt, sx, sy, qx, qy);
+    poly_edge<0, 2>(A, B, cnt, sx, sy, qx, qy); poly_edge<0, 3>(A, B, cnt, sx, sy, qx, qy);
+    poly_edge<1, 0>(A, B, cnt, sx, sy, qx, qy); poly_edge<1, 1>(A, B, cnt, sx, sy, qx, qy);
+    poly_edge<1, 2>(A, B, cnt, sx, sy, qx, qy); poly_edge<1, 3>(A, B, cnt, sx, sy, qx, qy);
+    poly_edge<2, 0>(A, B, cnt, sx, sy, qx, qy); poly_edge<2, 1>(A, B, cnt, sx, sy, qx, qy);
+    poly_edge<2, 2>(A, B, cnt, sx, sy, qx, qy); poly_edge<2, 3>(A, B, cnt, sx, sy, qx, qy);
+    poly_edge<3, 0>(A, B, cnt, sx, sy, qx, qy); poly_edge<3, 1>(A, B, cnt, sx, sy, qx, qy);
+    poly_edge<3, 2>(A, B, cnt, sx, sy, qx, qy); poly_edge<3, 3>(A, B, cnt, sx, sy, qx, qy);
+    // corners: the reference appends b's corner k (if in a), then a's corner k (if in b)
+    poly_append<16>(in_box2d(A, B.px[0], B.py[0]), B.px[0], B.py[0], cnt, sx, sy, qx, qy);
+    poly_append<17>(in_box2d(B, A.px[0], A.py[0]), A.px[0], A.py[0], cnt, sx, sy, qx, qy);
+    poly_append<18>(in_box2d(A, B.px[1], B.py[1]), B.px[1], B.py[1], cnt, sx, sy, qx, qy);
+    poly_append<19>(in_box2d(B, A.px[1], A.py[1]), A.px[1], A.py[1], cnt, sx, sy, qx, qy);
+    poly_append<20>(in_box2d(A, B.px[2], B.py[2]), B.px[2], B.py[2], cnt, sx, sy, qx, qy);
+    poly_append<21>(in_box2d(B, A.px[2], A.py[2]), A.px[2], A.py[2], cnt, sx, sy, qx, qy);
+    poly_append<22>(in_box2d(A, B.px[3], B.py[3]), B.px[3], B.py[3], cnt, sx, sy, qx, qy);
+    poly_append<23>(in_box2d(B, A.px[3], A.py[3]), A.px[3], A.py[3], cnt, sx, sy, qx, qy);
+    if (!__any(cnt > 0)) return 0.f;
+    sx /= cnt;
+    sy /= cnt;
+    // point_cmp's key, computed once per point
+#pragma unroll
+    for (int d = 0; d < kPoly; ++d) {
+        if (!__any(d < cnt)) break;
+        qk[d] = atan2f(qy[d] - sy, qx[d] - sx);
+    }
+    // The reference bubble-sorts with point_cmp (strict >): a stable sort by key.  A stable insertion sort (shift while strictly
+    // greater) yields the same permutation, so the shoelace sum below adds the same terms in the same order.
+#pragma unroll
+    for (int s = 1; s < kPoly; ++s) {
+        if (!__any(s < cnt)) break;
+        const float x = qx[s], y = qy[s], k = qk[s];
+        bool moving = s < cnt;
+#pragma unroll
+        for (int d = s; d >= 1; --d) {
+            const bool sh = moving && qk[d - 1] > k;
+            if (sh) { qx[d] = qx[d - 1]; qy[d] = qy[d - 1]; qk[d] = qk[d - 1]; }
+            else if (moving) { qx[d] = x; qy[d] = y; qk[d] = k; }
+            moving = sh;
+        }
+        if (moving) { qx[0] = x; qy[0] = y; qk[0] = k; }
+    }
+    // shoelace about the first point
+    float area = 0.f;
+#pragma unroll
+    for (int k = 0; k < kPoly - 1; ++k) {
+        if (!__any(k < cnt - 1)) break;
+        if (k < cnt - 1) {
+            const float ax = qx[k] - qx[0], ay = qy[k] - qy[0];
+            const float bx = qx[k + 1] - qx[0], by = qy[k + 1] - qy[0];
+            area += ax * by - ay * bx;
+        }
+    }
+    return (float)(fabsf(area) / 2.0);
+}
+
+__device__ __forceinline__ float iou_bev(const BoxG& A, const BoxG& B) {
+    const float s = box_overlap(A, B);
+    return s / fmaxf(A.area + B.area - s, kEps);
+}
+
+__device__ __forceinline__ float iou_normal(const BoxG& a, const BoxG& b) {
+    const float left = fmaxf(a.x1, b.x1), right = fminf(a.x2, b.x2);
+    const float top = fmaxf(a.y1, b.y1), bottom = fminf(a.y2, b.y2);
+    const float width = fmaxf(right - left, 0.f), height = fmaxf(bottom - top, 0.f);
+    const float inter = width * height;
+    return inter / fmaxf(a.area + b.area - inter, kEps);
+}
+
+// ---- pairwise [Na, Nb]: 64 columns (one per lane) x 64 rows (16 per wave, geometry in LDS) per workgroup
+enum { kOverlap = 0, kIou = 1, kIou3d = 2 };
+
+template <int kMode>
+__global__ __launch_bounds__(256) void pairwise_kernel(int Na, int Nb, const float* __restrict__ a, const float* __restrict__ b,
+                                                       float* __restrict__ out) {
+    constexpr int W = kMode == kIou3d ? 7 : 5;
+    __shared__ BoxG ra[64];
+    __shared__ float rh[64][3];             // 3D: y - h, y, h * w * l
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int a0 = blockIdx.y * 64, bi = blockIdx.x * 64 + lane;
+    if (tid < 64) {
+        const float* p = a + (int64_t)min(a0 + tid, Na - 1) * W;
+        ra[tid] = kMode == kIou3d ? box_geom7(p) : box_geom5(p);
+        if (kMode == kIou3d) { rh[tid][0] = p[1] - p[3]; rh[tid][1] = p[1]; rh[tid][2] = p[3] * p[4] * p[5]; }
+    }
+    const float* q = b + (int64_t)min(bi, Nb - 1) * W;
+    const BoxG cg = kMode == kIou3d ? box_geom7(q) : box_geom5(q);
+    float bmin = 0.f, bmax = 0.f, bvol = 0.f;
+    if (kMode == kIou3d) { bmin = q[1] - q[3]; bmax = q[1]; bvol = q[3] * q[4] * q[5]; }
+    __syncthreads();
+    for (int r = wave * 16; r < wave * 16 + 16; ++r) {
+        const int ai = a0 + r;
+        if (ai >= Na) break;                // uniform over the wave
+        float v;
+        if (kMode == kOverlap) {
+            v = box_overlap(ra[r], cg);
+        } else if (kMode == kIou) {
+            v = iou_bev(ra[r], cg);
+        } else {                            // boxes_iou3d_gpu after the BEV overlap, in its torch order
+            const float ov = box_overlap(ra[r], cg);
+            const float max_of_min = fmaxf(rh[r][0], bmin), min_of_max = fminf(rh[r][1], bmax);
+            const float oh = fmaxf(min_of_max - max_of_min, 0.f);
+            const float o3 = ov * oh;
+            v = o3 / fmaxf(rh[r][2] + bvol - o3, 1e-7f);
+        }
+        if (bi < Nb) out[(int64_t)ai * Nb + bi] = v;
+    }
+}
+
+// ---- NMS suppression mask of every batch row: mask[b, i, c] bit t = box c*64+t (> i) overlaps box i by more than thresh
+template <bool kNormal>
+__global__ __launch_bounds__(64) void nms_mask_kernel(int Nmax, int cw, const float* __restrict__ boxes, const int32_t* __restrict__ counts,
+                                                      float thresh, uint64_t* __restrict__ mask) {
+    const int cb = blockIdx.x, rb = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
+    if (cb < rb) return;                    // below the diagonal: never read
+    const int n = min(max(counts[b], 0), Nmax);
+    const int row0 = rb * 64, col0 = cb * 64;
+    if (col0 >= n) return;
+    const int rows = min(64, n - row0), cols = min(64, n - col0);
+    const float* bb = boxes + (int64_t)b * Nmax * 5;
+    __shared__ BoxG rg[64];
+    if (lane < rows) rg[lane] = box_geom5(bb + (int64_t)(row0 + lane) * 5);
+    const BoxG cg = box_geom5(bb + (int64_t)(col0 + min(lane, cols - 1)) * 5);
+    __syncthreads();
+    const bool diag = cb == rb;
+    uint64_t word = 0;
+    for (int r = 0; r < rows; ++r) {
+        const bool live = lane < cols && (!diag || lane > r);
+        const float v = kNormal ? iou_normal(rg[r], cg) : iou_bev(rg[r], cg);
+        const uint64_t bal = __ballot(live && v > thresh);
+        if (lane == r) word = bal;
+    }
+    if (lane < rows) mask[((int64_t)b * Nmax + row0 + lane) * cw + cb] = word;
+}
+
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src, 64), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// ---- the greedy walk of iou3d.cpp's nms_gpu, one wave per batch row: keep[b, k] = k-th kept position, num_keep[b]
+__global__ __launch_bounds__(64) void nms_walk_kernel(int Nmax, int cw, const int32_t* __restrict__ counts, const uint64_t* __restrict__ mask,
+                                                      int max_keep, int64_t* __restrict__ keep, int keep_stride, int32_t* __restrict__ num_keep) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int n = min(max(counts[b], 0), Nmax);
+    const int cwn = (n + 63) / 64;
+    const int lim = max_keep > 0 ? max_keep : n;
+    const uint64_t* mb = mask + (int64_t)b * Nmax * cw;
+    int64_t* kb = keep + (int64_t)b * keep_stride;
+    uint64_t remv[kWalkSlots];
+#pragma unroll
+    for (int k = 0; k < kWalkSlots; ++k) remv[k] = 0;
+    int kept = 0;
+    for (int c = 0; c < cwn && kept < lim; ++c) {
+        uint64_t mine = 0;
+#pragma unroll
+        for (int k = 0; k < kWalkSlots; ++k)
+            if (k == (c >> 6)) mine = remv[k];
+        uint64_t cur = shfl64(mine, c & 63);
+        const int nb = min(64, n - c * 64);
+        const uint64_t valid = nb == 64 ? ~0ull : ((1ull << nb) - 1ull);
+        uint64_t todo = ~cur & valid;
+        while (todo && kept < lim) {
+            const int bit = __ffsll((unsigned long long)todo) - 1;
+            const int i = c * 64 + bit;
+            if (lane == 0) kb[kept] = i;
+            ++kept;
+            const uint64_t* row = mb + (int64_t)i * cw;
+#pragma unroll
+            for (int k = 0; k < kWalkSlots; ++k) {
+                const int j = lane + 64 * k;
+                if (j >= c && j < cwn) remv[k] |= row[j];
+            }
+            cur |= row[c];
+            todo = ~cur & valid & ~((2ull << bit) - 1ull);     // bit 63: 2ull << 63 == 0, nothing left in this word
+        }
+    }
+    if (lane == 0) num_keep[b] = kept;
+}
+
+// ---- roipool3d
+// pt_in_box3d with its mixed precision: h / 2.0, l / 2.0, w / 2.0 are double; cos / sin of the float angle (cosa, sina)
+__device__ __forceinline__ bool pt_in_box3d(float x, float y, float z, const float* bx, float cosa, float sina) {
+    const float cx = bx[0], bottom_y = bx[1], cz = bx[2], h = bx[3], w = bx[4], l = bx[5];
+    const float cy = (float)((double)bottom_y - (double)h / 2.0);
+    if (fabsf(x - cx) > kMaxDis || (double)fabsf(y - cy) > (double)h / 2.0 || fabsf(z - cz) > kMaxDis) return false;
+    const float x_rot = (x - cx) * cosa + (z - cz) * (-sina);
+    const float z_rot = (x - cx) * sina + (z - cz) * cosa;
+    return ((double)x_rot >= (double)(-l) / 2.0) & ((double)x_rot <= (double)l / 2.0) & ((double)z_rot >= (double)(-w) / 2.0) &
+           ((double)z_rot <= (double)w / 2.0);
+}
+
+__global__ __launch_bounds__(kPoolThreads) void roipool3d_kernel(int N, int M, int C, int S, const float* __restrict__ xyz,
+                                                                 const float* __restrict__ boxes3d, const float* __restrict__ feat,
+                                                                 float* __restrict__ pooled, int32_t* __restrict__ empty_flag) {
+    __shared__ int32_t sidx[kMaxPoolSamples];
+    __shared__ int wcnt[kPoolThreads / 64];
+    const int bm = blockIdx.x, b = bm / M;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* bx = boxes3d + (int64_t)bm * 7;
+    const float cosa = cosf(bx[6]), sina = sinf(bx[6]);
+    const float* p = xyz + (int64_t)b * N * 3;
+    int cnt = 0;                            // block-uniform
+    for (int base = 0; base < N && cnt < S; base += kPoolThreads) {
+        const int k = base + tid;
+        const bool in = k < N && pt_in_box3d(p[(int64_t)k * 3 + 0], p[(int64_t)k * 3 + 1], p[(int64_t)k * 3 + 2], bx, cosa, sina);
+        const uint64_t bal = __ballot(in);
+        if (lane == 0) wcnt[wave] = __popcll(bal);
+        __syncthreads();
+        int before = 0, tot = 0;
+#pragma unroll
+        for (int w = 0; w < kPoolThreads / 64; ++w) {
+            const int c = wcnt[w];
+            before += w < wave ? c : 0;
+            tot += c;
+        }
+        const int pos = cnt + before + __popcll(bal & ((1ull << lane) - 1ull));
+        if (in && pos < S) sidx[pos] = k;
+        cnt += tot;
+        __syncthreads();
+    }
+    if (cnt == 0) {
+        if (tid == 0) empty_flag[bm] = 1;
+        return;
+    }
+    const int have = min(cnt, S);
+    const int row = 3 + C;
+    const float* fb = feat + (int64_t)b * N * C;
+    float* ob = pooled + (int64_t)bm * S * row;
+    for (int s = wave; s < S; s += kPoolThreads / 64) {
+        const int src = sidx[s % have];
+        float* o = ob + (int64_t)s * row;
+        for (int j = lane; j < row; j += 64)
+            o[j] = j < 3 ? p[(int64_t)src * 3 + j] : fb[(int64_t)src * C + (j - 3)];
+    }
+}
+
+__global__ __launch_bounds__(256) void pts_in_boxes3d_kernel(int N, int M, const float* __restrict__ xyz, const float* __restrict__ boxes3d,
+                                                             uint8_t* __restrict__ flags) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    const int m = blockIdx.y, b = blockIdx.z;
+    if (k >= N) return;
+    const float* bx = boxes3d + ((int64_t)b * M + m) * 7;
+    const float* q = xyz + ((int64_t)b * N + k) * 3;
+    flags[((int64_t)b * M + m) * N + k] = pt_in_box3d(q[0], q[1], q[2], bx, cosf(bx[6]), sinf(bx[6])) ? 1 : 0;
+}
+
+template <int kMode>
+int launch_pairwise(int Na, int Nb, const float* a, const float* b, float* out, void* stream) {
+    if (Na < 0 || Nb < 0) return -2;
+    if (Na == 0 || Nb == 0) return 0;
+    if (!a || !b || !out) return -1;
+    const int64_t gy = ((int64_t)Na + 63) / 64, gx = ((int64_t)Nb + 63) / 64;
+    if (gy > 65535 || gx > INT32_MAX) return -2;
+    hipLaunchKernelGGL(pairwise_kernel<kMode>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, Na, Nb, a, b, out);
+    return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int drc_box3d_bev(int Na, int Nb, const float* a, const float* b, int mode, float* out, void* stream) {
+    if (mode == 0) return launch_pairwise<kOverlap>(Na, Nb, a, b, out, stream);
+    if (mode == 1) return launch_pairwise<kIou>(Na, Nb, a, b, out, stream);
+    return -2;
+}
+
+extern "C" int drc_box3d_iou3d(int Na, int Nb, const float* a, const float* b, float* out, void* stream) {
+    return launch_pairwise<kIou3d>(Na, Nb, a, b, out, stream);
+}
+
+extern "C" int drc_box3d_nms(int B, int Nmax, const float* boxes, const int32_t* counts, float thresh, int normal, int max_keep, uint64_t* mask,
+                             int64_t* keep, int keep_stride, int32_t* num_keep, void* stream) {
+    if (B < 0 || Nmax < 0 || Nmax > kMaxNmsBoxes || B > 65535) return -2;
+    const int kmax = max_keep > 0 && max_keep < Nmax ? max_keep : Nmax;
+    if (keep_stride < kmax) return -2;
+    if (B == 0) return 0;
+    if (!counts || !num_keep || (Nmax > 0 && (!boxes || !mask || !keep))) return -1;
+    const int cw = (Nmax + 63) / 64;
+    hipStream_t st = (hipStream_t)stream;
+    if (Nmax > 0) {
+        const dim3 grid((unsigned)cw, (unsigned)cw, (unsigned)B);
+        if (normal)
+            hipLaunchKernelGGL(nms_mask_kernel<true>, grid, dim3(64), 0, st, Nmax, cw, boxes, counts, thresh, mask);
+        else
+            hipLaunchKernelGGL(nms_mask_kernel<false>, grid, dim3(64), 0, st, Nmax, cw, boxes, counts, thresh, mask);
+    }
+    hipLaunchKernelGGL(nms_walk_kernel, dim3((unsigned)B), dim3(64), 0, st, Nmax, cw, counts, mask, max_keep, keep, keep_stride, num_keep);
+    return (int)hipGetLastError();
+}
+
+extern "C" int drc_roipool3d_fwd(int B, int N, int M, int C, int S, const float* xyz, const float* boxes3d, const float* feat, float* pooled,
+                                 int32_t* empty_flag, void* stream) {
+    if (B < 0 || N < 0 || M < 0 || C < 0 || S < 0 || S > kMaxPoolSamples) return -2;
+    const int64_t blocks = (int64_t)B * M;
+    if (blocks == 0) return 0;
+    if (blocks > INT32_MAX) return -2;
+    if (!boxes3d || !empty_flag || (N > 0 && !xyz) || (N > 0 && C > 0 && !feat) || (S > 0 && !pooled)) return -1;
+    hipLaunchKernelGGL(roipool3d_kernel, dim3((unsigned)blocks), dim3(kPoolThreads), 0, (hipStream_t)stream, N, M, C, S, xyz, boxes3d, feat,
+                       pooled, empty_flag);
+    return (int)hipGetLastError();
+}
+
+extern "C" int drc_pts_in_boxes3d(int B, int N, int M, const float* xyz, const float* boxes3d, uint8_t* flags, void* stream) {
+    if (B < 0 || N < 0 || M < 0 || B > 65535 || M > 65535) return -2;
+    if ((int64_t)B * M * N == 0) return 0;
+    if (!xyz || !boxes3d || !flags) return -1;
+    hipLaunchKernelGGL(pts_in_boxes3d_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)M, (unsigned)B), dim3(256), 0, (hipStream_t)stream, N,
+                       M, xyz, boxes3d, flags);
+    return (int)hipGetLastError();
+}
+
+extern "C" int drc_box3d_max_pool_samples(void) { return kMaxPoolSamples; }

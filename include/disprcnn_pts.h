@@ -72,6 +72,31 @@ int drc_pn2_csr_bounds(int B, int E, int N, const int32_t* sorted_keys, int32_t*
 int drc_pn2_csr_scatter_add(int B, int C, int N, int K, int E, int per_col, const float* grad_out, const int32_t* perm,
                             const int32_t* seg_start, const int32_t* seg_end, const float* weight, float* grad_src, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * PointRCNN 3D box ops (point_rcnn/lib/utils/iou3d/src/iou3d_kernel.cu, roipool3d/src/roipool3d_kernel.cu).  fp32, evaluated in
+ * the reference's expression order.
+ * ------------------------------------------------------------------------------------- */
+/* a [Na,5], b [Nb,5] as [x1,y1,x2,y2,ry] -> out [Na,Nb]: mode 0 = rotated BEV overlap area (box_overlap), 1 = BEV IoU (iou_bev) */
+int drc_box3d_bev(int Na, int Nb, const float* a, const float* b, int mode, float* out, void* stream);
+/* a [Na,7], b [Nb,7] as [x,y,z,h,w,l,ry] -> out [Na,Nb]: boxes_iou3d_gpu (BEV conversion, overlap, height overlap, volumes, the
+ * clamp(min=1e-7) division) in one kernel */
+int drc_box3d_iou3d(int Na, int Nb, const float* a, const float* b, float* out, void* stream);
+/* Batched greedy NMS (nms_gpu / nms_normal_gpu of iou3d.cpp) of B rows at once.  boxes [B,Nmax,5], each row already in score
+ * order; counts [B] int32 (clamped to [0,Nmax]).  normal != 0: axis-aligned iou_normal, else rotated iou_bev; a box is suppressed
+ * when its IoU with a kept one is > thresh.  mask: B * Nmax * ceil(Nmax/64) words of workspace (contents need not be set).
+ * keep [B,keep_stride] int64 <- kept positions in row order, num_keep [B] int32 <- their count; a row stops after max_keep kept
+ * (max_keep <= 0: no limit), keep_stride >= min(max_keep, Nmax).  Nmax <= 32768.  Entries past num_keep are left untouched. */
+int drc_box3d_nms(int B, int Nmax, const float* boxes, const int32_t* counts, float thresh, int normal, int max_keep, uint64_t* mask,
+                  int64_t* keep, int keep_stride, int32_t* num_keep, void* stream);
+/* roipool3dLauncher: xyz [B,N,3], boxes3d [B,M,7] (already enlarged), feat [B,N,C] -> pooled [B,M,S,3+C] (xyz ++ feature of the
+ * first S in-box points in index order, repeated cyclically when fewer), empty_flag [B,M] int32 <- 1 for a box with no point (its
+ * rows and the other flags are left as the caller zeroed them).  In-box test: pt_in_box3d, max_dis 10.  S <= drc_box3d_max_pool_samples(). */
+int drc_roipool3d_fwd(int B, int N, int M, int C, int S, const float* xyz, const float* boxes3d, const float* feat, float* pooled,
+                      int32_t* empty_flag, void* stream);
+int drc_box3d_max_pool_samples(void);
+/* xyz [B,N,3], boxes3d [B,M,7] -> flags [B,M,N] uint8 (0/1): pt_in_box3d of every point and box */
+int drc_pts_in_boxes3d(int B, int N, int M, const float* xyz, const float* boxes3d, uint8_t* flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
