@@ -1,0 +1,149 @@
+"""Shared MLPs of PointNet++'s SA / FP modules on the fp32-MFMA kernels of libdisprcnn_pts.so (pts/pn2_mlp.hip).
+
+    sa_mlp_max(xyz, new_xyz, feats, idx, layers, out=None, c_off=0)      group -> MLP -> max over the neighbourhood, one kernel
+    pointwise_mlp(in0, in1, weight, bias, relu, out=None, c_off=0)       act(W . concat(in0, in1) + b), the concat never built
+
+A layer is a pair (W [Cout,Cin], b [Cout]) with BatchNorm already folded in (`fold_bn`), or a `Packed` pair made once by `pack`: the
+kernels read weights K-major, so a raw pair is transposed on the device at every call and a packed one is not.  GPU tensors, fp32,
+inference only (no autograd); there is no torch fallback.  `sa_mlp_max_unfused` is the same arithmetic done the long way
+(grouping_operation -> conv2d -> max) for tools/bench_rpn.py and the tests to compare against; the modules never call it.
+"""
+import torch
+import torch.nn.functional as F
+
+from .. import engine as E
+from ..pts import _lib
+
+
+class Packed:
+    """One layer as the kernels read it: wt [Cin,Cout] (K-major), bias [Cout]."""
+
+    __slots__ = ("wt", "bias", "cin", "cout")
+
+    def __init__(self, wt, bias):
+        self.wt, self.bias = wt, bias
+        self.cin, self.cout = int(wt.shape[0]), int(wt.shape[1])
+
+
+def pack(weight, bias):
+    """(W [Cout,Cin] or [Cout,Cin,1(,1)], b [Cout]) on the GPU -> Packed."""
+    w = weight.reshape(weight.shape[0], -1)
+    E.require_gpu(w, "pn2_mlp.pack")
+    E.require_gpu(bias, "pn2_mlp.pack")
+    if bias.shape != (w.shape[0],):
+        raise RuntimeError(f"pn2_mlp.pack: bias must be [{w.shape[0]}], got {tuple(bias.shape)}")
+    return Packed(w.detach().t().contiguous(), bias.detach().contiguous())
+
+
+def fold_bn(weight, bias, bn_weight, bn_bias, running_mean, running_var, eps):
+    """Fold an eval-mode BatchNorm into the 1x1 conv before it, in fp64 on the host, rounded once to fp32:
+    W' = W * g / sqrt(var + eps), b' = beta + (b - mean) * g / sqrt(var + eps)  (b = 0 when the conv has no bias).
+    -> (W' [Cout,Cin], b' [Cout]) fp32 CPU tensors."""
+    w = weight.detach().to("cpu", torch.float64).reshape(weight.shape[0], -1)
+    b = bias.detach().to("cpu", torch.float64) if bias is not None else torch.zeros(w.shape[0], dtype=torch.float64)
+    scale = bn_weight.detach().to("cpu", torch.float64) / torch.sqrt(running_var.detach().to("cpu", torch.float64) + eps)
+    w = w * scale.unsqueeze(1)
+    b = bn_bias.detach().to("cpu", torch.float64) + (b - running_mean.detach().to("cpu", torch.float64)) * scale
+    return w.float(), b.float()
+
+
+def _packed(layer):
+    return layer if isinstance(layer, Packed) else pack(layer[0], layer[1])
+
+
+def _out(out, shape, c_off, cout, dev, what):
+    B, _, L = shape
+    if out is None:
+        if c_off != 0:
+            raise RuntimeError(f"{what}: a channel offset needs the out buffer it points into")
+        return torch.empty((B, cout, L), dtype=torch.float32, device=dev)
+    E.require_gpu(out, what)
+    if out.dim() != 3 or out.shape[0] != B or out.shape[2] != L or not out.is_contiguous():
+        raise RuntimeError(f"{what}: out must be a contiguous [{B}, C_total, {L}] tensor, got {tuple(out.shape)}")
+    if c_off < 0 or c_off + cout > out.shape[1]:
+        raise RuntimeError(f"{what}: channels [{c_off}, {c_off + cout}) do not fit out's {out.shape[1]}")
+    return out
+
+
+def sa_mlp_max(xyz, new_xyz, feats, idx, layers, out=None, c_off=0):
+    """xyz (B,N,3), new_xyz (B,M,3), feats (B,C,N) or None, idx (B,M,ns) int32 from ball_query, layers: 1..3 of (W, b) / Packed.
+    -> out[b, c_off + c, m] = max_s MLP(concat(xyz[idx] - new_xyz, feats[:, idx]))[c], ReLU after every layer; out (B,C_total,M) is
+    allocated (C_total = the last width) unless given.  The input channel order is QueryAndGroup's with use_xyz."""
+    what = "sa_mlp_max"
+    E.require_gpu(xyz, what)
+    E.require_gpu(new_xyz, what)
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or new_xyz.dim() != 3 or new_xyz.shape[2] != 3 or new_xyz.shape[0] != xyz.shape[0]:
+        raise RuntimeError(f"{what}: xyz [B,N,3] and new_xyz [B,M,3] expected, got {tuple(xyz.shape)} and {tuple(new_xyz.shape)}")
+    B, N, _ = xyz.shape
+    M = new_xyz.shape[1]
+    C = 0
+    if feats is not None:
+        E.require_gpu(feats, what)
+        if feats.dim() != 3 or feats.shape[0] != B or feats.shape[2] != N:
+            raise RuntimeError(f"{what}: feats must be [{B},C,{N}], got {tuple(feats.shape)}")
+        C = feats.shape[1]
+        feats = feats.contiguous() if C else None
+    if not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 3 or idx.shape[:2] != (B, M):
+        raise RuntimeError(f"{what}: idx must be an int32 GPU tensor [{B},{M},ns], got {idx.dtype} {tuple(idx.shape)}")
+    ns = idx.shape[2]
+    if not 1 <= ns <= 64:
+        raise RuntimeError(f"{what}: nsample must be in 1..64, got {ns}")
+    ls = [_packed(l) for l in layers]
+    if not 1 <= len(ls) <= 3:
+        raise RuntimeError(f"{what}: 1 to 3 layers, got {len(ls)}")
+    cin = C + 3
+    for i, l in enumerate(ls):
+        if l.cin != cin:
+            raise RuntimeError(f"{what}: layer {i} takes {l.cin} channels, its input has {cin}")
+        cin = l.cout
+    out = _out(out, (B, cin, M), c_off, cin, xyz.device, what)
+    if B == 0 or M == 0:
+        return out
+    args = []
+    for i in range(3):
+        args += [E._ptr(ls[i].wt), E._ptr(ls[i].bias), ls[i].cout] if i < len(ls) else [E._ptr(None), E._ptr(None), 0]
+    st = _lib.lib().drc_pn2_sa_mlp_max_fwd(B, N, M, C, ns, E._ptr(xyz.contiguous()), E._ptr(new_xyz.contiguous()), E._ptr(feats),
+                                           E._ptr(idx.contiguous()), len(ls), *args, E._ptr(out), out.shape[1], c_off,
+                                           E._stream_ptr(xyz.device))
+    _lib.check(st, "drc_pn2_sa_mlp_max_fwd")
+    return out
+
+
+def pointwise_mlp(in0, in1, weight, bias, relu, out=None, c_off=0):
+    """in0 (B,C0,N), in1 (B,C1,N) or None, weight [Cout,C0+C1] (or a Packed, bias then ignored), bias [Cout]
+    -> out[b, c_off + c, n] = act(W . concat(in0, in1) + b), act = ReLU when `relu` else identity."""
+    what = "pointwise_mlp"
+    E.require_gpu(in0, what)
+    if in0.dim() != 3:
+        raise RuntimeError(f"{what}: in0 must be [B,C0,N], got {tuple(in0.shape)}")
+    B, C0, N = in0.shape
+    C1 = 0
+    if in1 is not None:
+        E.require_gpu(in1, what)
+        if in1.dim() != 3 or in1.shape[0] != B or in1.shape[2] != N:
+            raise RuntimeError(f"{what}: in1 must be [{B},C1,{N}], got {tuple(in1.shape)}")
+        C1 = in1.shape[1]
+        in1 = in1.contiguous() if C1 else None
+    l = weight if isinstance(weight, Packed) else pack(weight, bias)
+    if l.cin != C0 + C1 or C0 < 1:
+        raise RuntimeError(f"{what}: the layer takes {l.cin} channels, the inputs have {C0} + {C1}")
+    out = _out(out, (B, l.cout, N), c_off, l.cout, in0.device, what)
+    if B == 0 or N == 0:
+        return out
+    st = _lib.lib().drc_pn2_pointwise_mlp_fwd(B, N, C0, C1, E._ptr(in0.contiguous()), E._ptr(in1), E._ptr(l.wt), E._ptr(l.bias), l.cout,
+                                              1 if relu else 0, E._ptr(out), out.shape[1], c_off, E._stream_ptr(in0.device))
+    _lib.check(st, "drc_pn2_pointwise_mlp_fwd")
+    return out
+
+
+def sa_mlp_max_unfused(xyz, new_xyz, feats, idx, layers):
+    """The same result the materialising way: grouping_operation -> (B,C+3,M,ns) -> conv2d + ReLU per layer -> max.  For comparison
+    (tools/bench_rpn.py, tests) only."""
+    from .pointnet2 import grouping_operation
+    g = grouping_operation(xyz.transpose(1, 2).contiguous(), idx) - new_xyz.transpose(1, 2).unsqueeze(-1)
+    if feats is not None and feats.shape[1]:
+        g = torch.cat([g, grouping_operation(feats.contiguous(), idx)], dim=1)
+    for l in layers:
+        w, b = (l.wt.t(), l.bias) if isinstance(l, Packed) else (l[0].reshape(l[0].shape[0], -1), l[1])
+        g = F.relu(F.conv2d(g, w.reshape(w.shape[0], w.shape[1], 1, 1).contiguous(), b))
+    return g.max(dim=3)[0]

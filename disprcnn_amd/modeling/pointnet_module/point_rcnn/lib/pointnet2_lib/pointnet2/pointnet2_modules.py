@@ -1,0 +1,94 @@
+"""PointNet++ set-abstraction and feature-propagation modules (reference: pointnet2_lib/pointnet2/pointnet2_modules.py), inference
+only, on the HIP kernels: the index ops of layers/pointnet2.py and the fused shared MLPs of layers/pn2_mlp.py.
+
+An SA module is FPS -> gather -> per scale: ball query -> one fused group / MLP / max kernel that writes its scale's channels into
+the module's output, so neither the grouped tensor nor a torch.cat exists.  An FP module is three_nn -> weights -> three_interpolate
+-> the MLP, whose first layer reads the interpolated and the skip features as two inputs.  FPS and ball query read coordinates only,
+so every index equals the reference's.
+"""
+from typing import List
+
+import torch
+import torch.nn as nn
+
+from disprcnn_amd.layers import pn2_mlp
+from disprcnn_amd.layers import pointnet2 as pointnet2_utils
+from . import pytorch_utils as pt_utils
+
+
+class PointnetSAModuleMSG(nn.Module):
+    """Set abstraction with multi-scale grouping."""
+
+    def __init__(self, *, npoint: int, radii: List[float], nsamples: List[int], mlps: List[List[int]], bn: bool = True,
+                 use_xyz: bool = True, pool_method="max_pool", instance_norm=False):
+        super().__init__()
+        assert len(radii) == len(nsamples) == len(mlps)
+        if pool_method != "max_pool":
+            raise NotImplementedError(f"pool_method {pool_method!r}: the fused kernel takes the max over the neighbourhood")
+        if instance_norm:
+            raise NotImplementedError("instance_norm is not supported by the HIP shared-MLP kernels")
+        if not use_xyz:
+            raise NotImplementedError("use_xyz=False: the fused kernel always feeds the relative coordinates")
+        if npoint is None:
+            raise NotImplementedError("npoint=None (GroupAll) is not supported by the fused kernel")
+        self.npoint = npoint
+        self.pool_method = pool_method
+        self.groupers = nn.ModuleList()
+        self.mlps = nn.ModuleList()
+        for radius, nsample, spec in zip(radii, nsamples, mlps):
+            self.groupers.append(pointnet2_utils.QueryAndGroup(radius, nsample, use_xyz=use_xyz))
+            spec = list(spec)
+            spec[0] += 3
+            self.mlps.append(pt_utils.SharedMLP(spec, bn=bn, instance_norm=instance_norm))
+
+    def forward(self, xyz, features=None, new_xyz=None):
+        """xyz (B,N,3), features (B,C,N) or None -> new_xyz (B,npoint,3), new_features (B, sum of the scales' widths, npoint)."""
+        if self.training:
+            raise NotImplementedError("PointnetSAModuleMSG: the HIP forward is inference only; call .eval()")
+        with torch.no_grad():
+            if new_xyz is None:
+                fps_idx = pointnet2_utils.furthest_point_sample(xyz, self.npoint)
+                new_xyz = pointnet2_utils.gather_operation(xyz.transpose(1, 2).contiguous(), fps_idx).transpose(1, 2).contiguous()
+            folded = [m.folded() for m in self.mlps]
+            out = torch.empty((xyz.shape[0], sum(f[-1].cout for f in folded), new_xyz.shape[1]), dtype=torch.float32, device=xyz.device)
+            c_off = 0
+            for grouper, layers in zip(self.groupers, folded):
+                idx = pointnet2_utils.ball_query(grouper.radius, grouper.nsample, xyz, new_xyz)
+                pn2_mlp.sa_mlp_max(xyz, new_xyz, features, idx, layers, out=out, c_off=c_off)
+                c_off += layers[-1].cout
+        return new_xyz, out
+
+
+class PointnetSAModule(PointnetSAModuleMSG):
+    """Set abstraction with one scale."""
+
+    def __init__(self, *, mlp: List[int], npoint: int = None, radius: float = None, nsample: int = None, bn: bool = True,
+                 use_xyz: bool = True, pool_method="max_pool", instance_norm=False):
+        super().__init__(mlps=[mlp], npoint=npoint, radii=[radius], nsamples=[nsample], bn=bn, use_xyz=use_xyz,
+                         pool_method=pool_method, instance_norm=instance_norm)
+
+
+class PointnetFPModule(nn.Module):
+    """Feature propagation: three-nearest-neighbour interpolation of the coarser level's features, then a shared MLP."""
+
+    def __init__(self, *, mlp: List[int], bn: bool = True):
+        super().__init__()
+        self.mlp = pt_utils.SharedMLP(mlp, bn=bn)
+
+    def forward(self, unknown, known, unknow_feats, known_feats):
+        """unknown (B,n,3), known (B,m,3), unknow_feats (B,C1,n) or None, known_feats (B,C2,m) -> (B, mlp[-1], n)."""
+        if self.training:
+            raise NotImplementedError("PointnetFPModule: the HIP forward is inference only; call .eval()")
+        with torch.no_grad():
+            if known is not None:
+                dist, idx = pointnet2_utils.three_nn(unknown, known)
+                inv = 1.0 / (dist + 1e-8)                      # inverse-distance weights, normalised over the three neighbours
+                weight = inv / inv.sum(dim=2, keepdim=True)
+                x = pointnet2_utils.three_interpolate(known_feats.contiguous(), idx, weight)
+            else:
+                x = known_feats.expand(*known_feats.size()[0:2], unknown.size(1)).contiguous()
+            skip = unknow_feats
+            for layer in self.mlp:
+                x = pn2_mlp.pointwise_mlp(x, skip, layer.folded(), None, layer.relu)
+                skip = None
+        return x

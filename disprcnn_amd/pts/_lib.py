@@ -33,6 +33,10 @@ _SIGS = {
     "drc_roipool3d_fwd": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "drc_box3d_max_pool_samples": (_I, []),
     "drc_pts_in_boxes3d": (_I, [_I, _I, _I, _P, _P, _P, _P]),
+    "drc_pn2_sa_mlp_max_fwd": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P]),
+    "drc_pn2_pointwise_mlp_fwd": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _I, _I, _P]),
+    "drc_rpn_points_depth": (_I, [_L, _P, _P, _P]),
+    "drc_rpn_decode_proposals": (_I, [_L, _I, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

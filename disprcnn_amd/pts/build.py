@@ -12,7 +12,7 @@ import sys
 from ..csrc.build import FLAGS, HIPCC
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["points.hip", "pointnet2.hip", "boxes3d.hip"]
+SOURCES = ["points.hip", "pointnet2.hip", "boxes3d.hip", "pn2_mlp.hip"]
 HEADER = os.path.join(HERE, "..", "..", "include", "disprcnn_pts.h")
 LIB = os.path.join(HERE, "libdisprcnn_pts.so")
 MAX_JOBS = 16

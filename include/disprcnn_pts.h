@@ -97,6 +97,36 @@ int drc_box3d_max_pool_samples(void);
 /* xyz [B,N,3], boxes3d [B,M,7] -> flags [B,M,N] uint8 (0/1): pt_in_box3d of every point and box */
 int drc_pts_in_boxes3d(int B, int N, int M, const float* xyz, const float* boxes3d, uint8_t* flags, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * PointRCNN RPN: shared MLPs on fp32 MFMA (v_mfma_f32_32x32x2_f32, fp32 accumulate) and the proposal decode (pts/pn2_mlp.hip).
+ *
+ * Weights are BatchNorm-folded by the caller and passed K-MAJOR: wt_l [Cin_l, Cout_l] (the transpose of the conv weight
+ * W_l [Cout_l, Cin_l]), bias b_l [Cout_l].  Outputs go into a [B, c_total, *] buffer at channel offset c_off.
+ * ------------------------------------------------------------------------------------- */
+/* Fused group -> shared MLP (ReLU after every layer) -> max over the neighbourhood:
+ *   out[b, c_off + c, m] = max_s MLP(concat(xyz[b, idx[b,m,s]] - new_xyz[b,m], feats[b, :, idx[b,m,s]]))[c]
+ * xyz [B,N,3], new_xyz [B,M,3], feats [B,C,N] (null when C = 0), idx [B,M,nsample] int32 (values are clamped to [0,N)).
+ * n_layers in 1..3 (unused layers: null, 0); Cin_0 = C + 3, Cin_l = Cout_{l-1}.  1 <= nsample <= 64; any C >= 0 and Cout >= 1 for the
+ * last layer; a hidden layer's width is bounded by the LDS image that holds it (512).  -3: widths not supported. */
+int drc_pn2_sa_mlp_max_fwd(int B, int N, int M, int C, int nsample, const float* xyz, const float* new_xyz, const float* feats,
+                           const int32_t* idx, int n_layers, const float* wt0, const float* b0, int cout0, const float* wt1, const float* b1,
+                           int cout1, const float* wt2, const float* b2, int cout2, float* out, int c_total, int c_off, void* stream);
+/* out[b, c_off + c, n] = act(sum_k wt[k, c] * concat(in0 [B,C0,N], in1 [B,C1,N])[b, k, n] + bias[c]); in1 null when C1 = 0;
+ * relu != 0: ReLU, else no activation. */
+int drc_pn2_pointwise_mlp_fwd(int B, int N, int C0, int C1, const float* in0, const float* in1, const float* wt, const float* bias, int cout,
+                              int relu, float* out, int c_total, int c_off, void* stream);
+/* decode_bbox_target in the RPN's form (get_y_by_bin = False, get_ry_fine = False; first-maximum argmax), then y += h / 2, and
+ * boxes3d_to_bev in the same pass: xyz [n,3], reg [n,R] -> boxes [n,7] (x, y, z, h, w, l, ry), bev [n,5] (x1, y1, x2, y2, ry).
+ * R = per_loc_bin_num * (xz_fine ? 4 : 2) + 1 + 2 * num_head_bin + 3.  The constants are the reference's Python doubles rounded to
+ * fp32 by the caller: half_bin = loc_bin_size / 2, angle_per_class = 2 pi / num_head_bin, half_angle = angle_per_class / 2.
+ * fp32 in the reference's expression order (the library is built without FP contraction); the wrap is torch's remainder. */
+int drc_rpn_decode_proposals(int64_t n, int R, const float* xyz, const float* reg, int per_loc_bin_num, int num_head_bin, int xz_fine,
+                             float loc_bin_size, float half_bin, float loc_scope, float angle_per_class, float half_angle, float two_pi,
+                             float pi, float anchor_h, float anchor_w, float anchor_l, float* boxes, float* bev, void* stream);
+/* xyz [n,3] -> out [n] = |p| (RPN's pts_depth): sqrt(fma(z, z, fma(y, y, x * x))), the rounding of torch's CPU norm reduction, which
+ * the reference's recordings were made with; bit-identical on every device. */
+int drc_rpn_points_depth(int64_t n, const float* xyz, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
