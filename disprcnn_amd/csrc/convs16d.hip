@@ -11,6 +11,12 @@
 //     (9 taps, 27 MFMAs) feeds one accumulator, an odd plane (18 taps, 54 MFMAs) finishes it and opens the next; a pair of planes = one
 //     output plane = 81 MFMAs per wave, published after the odd step and finalized in the shadow of the next even step's MFMAs.
 //   * no residual (the reference's stride-2 layers have none).
+//   * the columns of a workgroup are ONE stream of steps, as in convs16.hip: the slab ring runs RING - 1 planes ahead into the next
+//     column(s), the even step of a column's plane 0 finalizes the LAST plane of the previous column (its base, its lane mask; the
+//     exchange buffer and the accumulator alternate with the FLAT output-plane index: Do may be odd), one cold start before the first
+//     column and one drain step after the last.  The odd step of a column's last plane runs only its kd = 2 taps (there is no plane Do
+//     for the kd = 0 taps to open, and the other accumulator must be clear for the next column).  Same products, same order of
+//     summation as the column-by-column walk: bit-identical outputs.
 //   * DEI (de-interleaved slab rows): a tap reads every second staged voxel, i.e. 16-byte LDS slots at a stride of two -- 14 lanes on 8 of the
 //     16 slots of a bank row, a 2-way conflict whatever the lane order (42-59 % of these kernels' LDS cycles, profiles/r5_pmc.md at 5429fbb).
 //     The LDS-DMA lanes therefore gather a staged row as [even columns | odd columns] (each lane's global address is its own), so that tap
@@ -138,138 +144,193 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
     for (int e = 0; e < OWN; ++e) { og.see_raw(sc[e], 3.0e38f); og.see_raw(sh[e], 3.0e38f); }      // a NaN / Inf folded BN parameter
 
-    for (unsigned it = 0;; ++it) {
+    // ---- the columns of this workgroup, in order (XCD-aware, as in convs16.hip).  The pipeline runs through them WITHOUT draining at a
+    // column's end: ONE flat sequence of steps (column, input plane), one cold start before the first, one drain step after the last.
+    // The slab cursor runs RING - 1 steps ahead of the MFMA step, into the next column(s); the first even step of a column finalizes the
+    // LAST output plane of the previous one.
+    struct Col { unsigned n; int y0, x0; bool valid; };
+    auto col_of = [&](unsigned it) __attribute__((always_inline)) {
         const unsigned j = it * per_xcd + qx;
         const unsigned nl = j / cols_unit;
-        const unsigned n = nl * 8 + xcd;
-        if (n >= (unsigned)p.N) break;
         const unsigned rem = j - nl * cols_unit;
         const int yb = (int)(rem / n_xt), xt = (int)(rem - (unsigned)yb * n_xt);
-        const int y0 = yb * RPW * RT, x0 = xt * WT;          // output tile origin
-
-        // staged input rows start at input row 2*y0 - 1 = padded row 2*y0, columns at padded column 2*x0
-        const char* xcol = (const char*)p.x + (long)n * i_nB + (long)(2 * y0) * i_rowB + (long)(2 * x0) * 16;
-        auto stage = [&](int plane, int slot) __attribute__((always_inline)) {       // logical input plane (clamped) -> ring slot
-            const int pl = plane < Di ? plane : Di - 1;
-            char* dst = ring + slot * SLAB;
-#pragma unroll
-            for (int ci = 0; ci < CBI * 2; ++ci) {
-                const int cc = ci * 4 + wave;                            // this wave's chunk planes (cb*8 + c): every fourth
-                const int cb = cc >> 3, c = cc & 7;
-                const char* src = xcol + (long)cb * i_cbB + (long)(pl + 1) * i_planeB + (long)c * (Wpi * 16);
-#pragma unroll
-                for (int h = 0; h < NPI; ++h)
-                    __builtin_amdgcn_global_load_lds(GLOBAL_PTR(src + srcoff[h]), LDS_PTR(dst + cc * CPB + h * 1024), 16, 0, 0);
-            }
-        };
-        const __amdgpu_buffer_rsrc_t y16r = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)p.y16 + (long)n * o_nB), 0, 0x7FFFFF00, 0x00020000);
-        const int yl = y0 + rs * RT + rl;
-        const bool lane_ok = tln.ok && yl < Ho && x0 + xl < Wo;
-        unsigned o16;
+        Col c;
+        c.n = nl * 8 + xcd;
+        c.valid = c.n < (unsigned)p.N;
+        c.y0 = yb * RPW * RT;                                    // output tile origin
+        c.x0 = xt * WT;
+        return c;
+    };
+    // output side of a column: the unit's base (the buffer resource is made from it where it is used) and this lane's voxel offset in
+    // output plane 0 (padded + 1).  Past the last column: valid = ok = false (all dropped)
+    struct Ctx { char* yb; unsigned o16; bool ok, valid; };
+    auto ctx_of = [&](const Col& c) __attribute__((always_inline)) {
+        Ctx q;
+        q.yb = (char*)p.y16 + (long)(c.valid ? c.n : 0u) * o_nB;
+        const int yl = c.y0 + rs * RT + rl;
+        q.valid = c.valid;
+        q.ok = c.valid && tln.ok && yl < Ho && c.x0 + xl < Wo;
         if constexpr (KW == 2)
-            o16 = (unsigned)((long)ct * o_cbB + o_planeB + (long)(yl + 1) * o_rowB + (long)(k * 2 + g) * (Wpo * 16) + (long)(x0 + xl + 1) * 16);
+            q.o16 = (unsigned)((long)ct * o_cbB + o_planeB + (long)(yl + 1) * o_rowB + (long)(k * 2 + g) * (Wpo * 16) + (long)(c.x0 + xl + 1) * 16);
         else
-            o16 = (unsigned)((long)ct * o_cbB + o_planeB + (long)(yl + 1) * o_rowB + (long)((k >> 1) * 2 + g) * (Wpo * 16) + (long)(x0 + xl + 1) * 16 + (k & 1) * 8);
-        const unsigned lo_off = (unsigned)(4 * Wpo * 16);
+            q.o16 = (unsigned)((long)ct * o_cbB + o_planeB + (long)(yl + 1) * o_rowB + (long)((k >> 1) * 2 + g) * (Wpo * 16) + (long)(c.x0 + xl + 1) * 16 + (k & 1) * 8);
+        return q;
+    };
+    const unsigned lo_off = (unsigned)(4 * Wpo * 16);
 
-        f32x16 acc[2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][e] = 0.f;
+    unsigned it_c = 0;                                           // the step's column
+    {
+        const Col c0 = col_of(0);
+        if (!c0.valid) {
+            og.flush(p.ovf);
+            return;
+        }
+    }
+    Ctx cur = ctx_of(col_of(0)), prev = cur;
+    prev.ok = prev.valid = false;
+    int zo = 0;                                                  // ... and its output plane
 
+    // ---- slab cursor: staged input rows start at input row 2*y0 - 1 = padded row 2*y0, columns at padded column 2*x0.  stage_next()
+    // issues the slab of the cursor's (column, plane) and moves on through the flat sequence -- into the next column at a column's end;
+    // past the last column it stays on the last slab (re-loaded into a slot nobody reads: the count of vector-memory instructions per
+    // step is fixed)
+    auto xcol_of = [&](const Col& c) __attribute__((always_inline)) {
+        return (const char*)p.x + (long)c.n * i_nB + (long)(2 * c.y0) * i_rowB + (long)(2 * c.x0) * 16;
+    };
+    unsigned it_s = 0;
+    int pl_s = 0;
+    const char* xcol_s = xcol_of(col_of(0));
+    auto stage_next = [&](int slot) __attribute__((always_inline)) {
+        char* dst = ring + slot * SLAB;
+#pragma unroll
+        for (int ci = 0; ci < CBI * 2; ++ci) {
+            const int cc = ci * 4 + wave;                            // this wave's chunk planes (cb*8 + c): every fourth
+            const int cb = cc >> 3, c = cc & 7;
+            const char* src = xcol_s + (long)cb * i_cbB + (long)(pl_s + 1) * i_planeB + (long)c * (Wpi * 16);
+#pragma unroll
+            for (int h = 0; h < NPI; ++h)
+                __builtin_amdgcn_global_load_lds(GLOBAL_PTR(src + srcoff[h]), LDS_PTR(dst + cc * CPB + h * 1024), 16, 0, 0);
+        }
+        if (pl_s + 1 < Di) {
+            ++pl_s;
+        } else {
+            const Col c = col_of(it_s + 1);
+            if (c.valid) {
+                ++it_s;
+                pl_s = 0;
+                xcol_s = xcol_of(c);
+            }
+        }
+    };
+
+    f32x16 acc[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[a][e] = 0.f;
+
+    // ---- the one cold start
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(S16_WAITCNT(63, 0));
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int s_ = 0; s_ + 1 < RING; ++s_) stage_next(s_);
+    int slot = 0;                                         // ring slot of the current input plane
+
+    // one input plane of column `cur`; A: the parity of the FLAT output-plane index (accumulator and exchange buffer).
+    //   ODD = false: plane 2zo, taps kd = 1 into acc[A]; finalizes meanwhile the output plane before it in the flat sequence: zo-1, or at
+    //                zo = 0 the LAST plane of `prev`.  COMPUTE = false: the drain step after the last column (`cur` is past the end).
+    //   ODD = true : plane 2zo+1, taps kd = 2 into acc[A] (complete: published) and kd = 0 into acc[B] (plane zo+1; not at a column's
+    //                last plane: there is no plane Do, and acc[B] must be clear for the next column's plane 0).
+    auto step = [&](auto AT, auto ODDT, auto COMPT) __attribute__((always_inline)) {
+        constexpr int A = decltype(AT)::value, B = A ^ 1;
+        constexpr bool ODD = decltype(ODDT)::value, COMPUTE = decltype(COMPT)::value;
+        // the slab of this plane landed: in flight behind it may be the RING-2 younger slabs and the previous step's stores
         asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(S16_WAITCNT(63, 0));
+        __builtin_amdgcn_s_waitcnt(S16_WAITCNT((RING - 2) * NL + (ODD ? NS : 0), 0));
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-#pragma unroll
-        for (int s_ = 0; s_ + 1 < RING; ++s_) stage(s_, s_);
-        int slot = 0;                                         // ring slot of the current input plane
-
-        // one input plane.  ODD = false: plane 2zo, taps kd = 1 into acc[A]; finalizes output plane zo-1 meanwhile.
-        //                   ODD = true : plane 2zo+1, taps kd = 2 into acc[A] (complete: published) and kd = 0 into acc[B] (plane zo+1).
-        auto step = [&](int zi, int zo, auto AT, auto ODDT, auto COMPT) __attribute__((always_inline)) {
-            constexpr int A = decltype(AT)::value, B = A ^ 1;
-            constexpr bool ODD = decltype(ODDT)::value, COMPUTE = decltype(COMPT)::value;
-            // the slab of plane zi landed: in flight behind it may be the RING-2 younger slabs and the previous step's stores
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_waitcnt(S16_WAITCNT((RING - 2) * NL + (ODD ? NS : 0), 0));
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            {
-                int ns = slot + RING - 1; ns = ns >= RING ? ns - RING : ns;
-                stage(zi + RING - 1, ns);                    // the slot of plane zi-1: free since the barrier
-            }
-            const __attribute__((address_space(3))) char* sb = ringl + slot * SLAB + bfrag;
-            if constexpr (!ODD) {
-                // ---- finalize plane zo-1 (partial sums of the K slices, this wave's couts) in the shadow of the 27 MFMAs
-                f32x4 part[4];
-                const char* xb = xchg + ((zo - 1) & 1) * (4 * XW) + (r * KW) * XW + lane * 16;
-                if constexpr (KW == 2) {
-                    part[0] = *(const f32x4*)(xb + (k * 2) * 1024);
-                    part[1] = *(const f32x4*)(xb + XW + (k * 2) * 1024);
-                    part[2] = *(const f32x4*)(xb + (k * 2 + 1) * 1024);
-                    part[3] = *(const f32x4*)(xb + XW + (k * 2 + 1) * 1024);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) part[q] = *(const f32x4*)(xb + q * XW + k * 1024);
-                }
-                _Float16 vh[OWN], vl[OWN];
-                const unsigned long long og_keep = S16Ovf::lanes(lane_ok && zo >= 1);      // dropped lanes / the step before the first plane: not values of the map
-                auto fin = [&](int e) __attribute__((always_inline)) {
-                    float s_;
-                    if constexpr (KW == 2) s_ = part[(e >> 2) * 2][e & 3] + part[(e >> 2) * 2 + 1][e & 3];
-                    else s_ = (part[0][e] + part[1][e]) + (part[2][e] + part[3][e]);
-                    float x_ = fmaxf(s_ * sc[e] + sh[e], relu_lo);
-                    x_ = fminf(x_, 65504.f);
-                    og.see(x_, og_keep);
-                    vh[e] = (_Float16)x_;
-                    vl[e] = (_Float16)(x_ - (float)vh[e]);
-                };
-                f16x8 bh[2], bl[2];
-                if constexpr (COMPUTE) {
-                    bh[0] = *(lds_frag*)(sb);
-                    bl[0] = *(lds_frag*)(sb + 4 * CPB);
-                }
-#pragma unroll
-                for (int q = 0; q < 9; ++q) {
-                    if constexpr (COMPUTE) {
-                        const int kh = q / 3, kw = q - kh * 3;
-                        if (q + 1 < 9) {
-                            const int kh1 = (q + 1) / 3, kw1 = (q + 1) - kh1 * 3;
-                            bh[(q + 1) & 1] = *(lds_frag*)(sb + tapoff(kh1, kw1));
-                            bl[(q + 1) & 1] = *(lds_frag*)(sb + 4 * CPB + tapoff(kh1, kw1));
-                        }
-                        const f16x8 h_ = bh[q & 1], l_ = bl[q & 1];
-                        const int t1 = 9 + kh * 3 + kw;
-                        acc[A] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[t1], h_, acc[A], 0, 0, 0);
-                        acc[A] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[t1], l_, acc[A], 0, 0, 0);
-                        acc[A] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[t1], h_, acc[A], 0, 0, 0);
-                    }
-                    if (q < OWN) fin(q);
-                    if (q == OWN || (OWN == 8 && q == 8)) {
-                        const bool ok = lane_ok && zo >= 1;
-                        const unsigned po = ok ? (unsigned)((long)(zo - 1) * o_planeB) : 0x80000000u;
-                        if constexpr (KW == 2) {
-                            f16x8 hi, lo;
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) { hi[e] = vh[e]; lo[e] = vl[e]; }
-                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), y16r, o16 + po, 0, 0);
-                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), y16r, o16 + lo_off + po, 0, 0);
-                        } else {
-                            f16x4 hi, lo;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) { hi[e] = vh[e]; lo[e] = vl[e]; }
-                            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hi), y16r, o16 + po, 0, 0);
-                            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, lo), y16r, o16 + lo_off + po, 0, 0);
-                        }
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+        {
+            int ns = slot + RING - 1; ns = ns >= RING ? ns - RING : ns;
+            stage_next(ns);                                  // the slot of the previous plane: free since the barrier
+        }
+        const __attribute__((address_space(3))) char* sb = ringl + slot * SLAB + bfrag;
+        if constexpr (!ODD) {
+            // ---- finalize the previous plane (partial sums of the K slices, this wave's couts) in the shadow of the 27 MFMAs
+            const bool first = zo == 0;
+            const bool ok = first ? prev.ok : cur.ok;        // dropped lanes / the step before the workgroup's first plane: not values of the map
+            const unsigned o16 = first ? prev.o16 : cur.o16;
+            const int zf = first ? Do - 1 : zo - 1;
+            const __amdgpu_buffer_rsrc_t y16r = __builtin_amdgcn_make_buffer_rsrc((void*)(first ? prev.yb : cur.yb), 0, 0x7FFFFF00, 0x00020000);
+            f32x4 part[4];
+            const char* xb = xchg + B * (4 * XW) + (r * KW) * XW + lane * 16;
+            if constexpr (KW == 2) {
+                part[0] = *(const f32x4*)(xb + (k * 2) * 1024);
+                part[1] = *(const f32x4*)(xb + XW + (k * 2) * 1024);
+                part[2] = *(const f32x4*)(xb + (k * 2 + 1) * 1024);
+                part[3] = *(const f32x4*)(xb + XW + (k * 2 + 1) * 1024);
             } else {
-                f16x8 bh[2], bl[2];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) part[q] = *(const f32x4*)(xb + q * XW + k * 1024);
+            }
+            _Float16 vh[OWN], vl[OWN];
+            const unsigned long long og_keep = S16Ovf::lanes(ok);
+            auto fin = [&](int e) __attribute__((always_inline)) {
+                float s_;
+                if constexpr (KW == 2) s_ = part[(e >> 2) * 2][e & 3] + part[(e >> 2) * 2 + 1][e & 3];
+                else s_ = (part[0][e] + part[1][e]) + (part[2][e] + part[3][e]);
+                float x_ = fmaxf(s_ * sc[e] + sh[e], relu_lo);
+                x_ = fminf(x_, 65504.f);
+                og.see(x_, og_keep);
+                vh[e] = (_Float16)x_;
+                vl[e] = (_Float16)(x_ - (float)vh[e]);
+            };
+            f16x8 bh[2], bl[2];
+            if constexpr (COMPUTE) {
                 bh[0] = *(lds_frag*)(sb);
                 bl[0] = *(lds_frag*)(sb + 4 * CPB);
+            }
+#pragma unroll
+            for (int q = 0; q < 9; ++q) {
+                if constexpr (COMPUTE) {
+                    const int kh = q / 3, kw = q - kh * 3;
+                    if (q + 1 < 9) {
+                        const int kh1 = (q + 1) / 3, kw1 = (q + 1) - kh1 * 3;
+                        bh[(q + 1) & 1] = *(lds_frag*)(sb + tapoff(kh1, kw1));
+                        bl[(q + 1) & 1] = *(lds_frag*)(sb + 4 * CPB + tapoff(kh1, kw1));
+                    }
+                    const f16x8 h_ = bh[q & 1], l_ = bl[q & 1];
+                    const int t1 = 9 + kh * 3 + kw;
+                    acc[A] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[t1], h_, acc[A], 0, 0, 0);
+                    acc[A] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[t1], l_, acc[A], 0, 0, 0);
+                    acc[A] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[t1], h_, acc[A], 0, 0, 0);
+                }
+                if (q < OWN) fin(q);
+                if (q == OWN || (OWN == 8 && q == 8)) {
+                    const unsigned po = ok ? (unsigned)((long)zf * o_planeB) : 0x80000000u;
+                    if constexpr (KW == 2) {
+                        f16x8 hi, lo;
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) { hi[e] = vh[e]; lo[e] = vl[e]; }
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), y16r, o16 + po, 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), y16r, o16 + lo_off + po, 0, 0);
+                    } else {
+                        f16x4 hi, lo;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { hi[e] = vh[e]; lo[e] = vl[e]; }
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hi), y16r, o16 + po, 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, lo), y16r, o16 + lo_off + po, 0, 0);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+            const bool last = zo + 1 == Do;
+            f16x8 bh[2], bl[2];
+            bh[0] = *(lds_frag*)(sb);
+            bl[0] = *(lds_frag*)(sb + 4 * CPB);
+            if (!last) {
 #pragma unroll
                 for (int q = 0; q < 9; ++q) {
                     const int kh = q / 3, kw = q - kh * 3;
@@ -288,35 +349,60 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     acc[B] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[t0], h_, acc[B], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                // output plane zo complete: publish, clear
-                const f32x16 a = acc[A];
-                char* xb = xchg + (zo & 1) * (4 * XW) + wave * XW + lane * 16;
+            } else {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) *(f32x4*)(xb + q * 1024) = (f32x4){a[q * 4], a[q * 4 + 1], a[q * 4 + 2], a[q * 4 + 3]};
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[A][e] = 0.f;
+                for (int q = 0; q < 9; ++q) {
+                    const int kh = q / 3, kw = q - kh * 3;
+                    if (q + 1 < 9) {
+                        const int kh1 = (q + 1) / 3, kw1 = (q + 1) - kh1 * 3;
+                        bh[(q + 1) & 1] = *(lds_frag*)(sb + tapoff(kh1, kw1));
+                        bl[(q + 1) & 1] = *(lds_frag*)(sb + 4 * CPB + tapoff(kh1, kw1));
+                    }
+                    const f16x8 h_ = bh[q & 1], l_ = bl[q & 1];
+                    const int t2 = 18 + kh * 3 + kw;
+                    acc[A] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[t2], h_, acc[A], 0, 0, 0);
+                    acc[A] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[t2], l_, acc[A], 0, 0, 0);
+                    acc[A] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[t2], h_, acc[A], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
-            slot = slot + 1 == RING ? 0 : slot + 1;
-        };
-        using F = std::false_type;
-        using T = std::true_type;
-        using I0 = std::integral_constant<int, 0>;
-        using I1 = std::integral_constant<int, 1>;
-        int zo = 0;
+            // output plane zo complete: publish, clear
+            const f32x16 a = acc[A];
+            char* xb = xchg + A * (4 * XW) + wave * XW + lane * 16;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) *(f32x4*)(xb + q * 1024) = (f32x4){a[q * 4], a[q * 4 + 1], a[q * 4 + 2], a[q * 4 + 3]};
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[A][e] = 0.f;
+            // on to the next output plane of the flat sequence
+            if (last) {
+                zo = 0;
+                prev = cur;
+                ++it_c;
+                cur = ctx_of(col_of(it_c));
+            } else {
+                ++zo;
+            }
+        }
+        slot = slot + 1 == RING ? 0 : slot + 1;
+    };
+    using F = std::false_type;
+    using T = std::true_type;
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
 #pragma unroll 1
-        for (; zo + 1 < Do; zo += 2) {
-            step(2 * zo, zo, I0{}, F{}, T{});
-            step(2 * zo + 1, zo, I0{}, T{}, T{});
-            step(2 * zo + 2, zo + 1, I1{}, F{}, T{});
-            step(2 * zo + 3, zo + 1, I1{}, T{}, T{});
+    for (;;) {
+        if (!cur.valid) {
+            step(I0{}, F{}, F{});                            // drain: finalize the last plane (an even step without MFMAs)
+            break;
         }
-        if (zo < Do) {
-            step(2 * zo, zo, I0{}, F{}, T{});
-            step(2 * zo + 1, zo, I0{}, T{}, T{});
-            ++zo;
+        step(I0{}, F{}, T{});
+        step(I0{}, T{}, T{});
+        if (!cur.valid) {
+            step(I1{}, F{}, F{});
+            break;
         }
-        // drain: finalize the last plane (an even step without MFMAs)
-        step(2 * zo, zo, I0{}, F{}, F{});
+        step(I1{}, F{}, T{});
+        step(I1{}, T{}, T{});
     }
     og.flush(p.ovf);
 }

@@ -14,6 +14,13 @@
 // voxels (the shifts are {0, +1}^2): one LDS-DMA instruction per 8-channel chunk plane.  A step runs the taps that COMPLETE accumulators
 // first; their epilogues (BN, residual, ReLU, hi/lo split, 16-byte stores of whole chunks) issue in the shadow of the taps that open the
 // next plane's accumulators.
+//
+// The columns of a workgroup are ONE stream of steps (as in convs16.hip): the slab ring runs RING - 1 steps ahead into the next column(s),
+// the residual requests one step ahead, and step zi = 0 of a column closes the last odd output plane 2 Di - 1 of the PREVIOUS column (through
+// that column's bases and lane mask) in the epilogue slot that has nothing of its own to close.  One cold start before the first column,
+// one drain step (no MFMA) after the last.  The accumulator / residual-set parity is that of the flat step index (Di may be odd); the
+// kd = 0 taps of a column's plane 0 (output plane -1) are not run, so the accumulator they would touch still holds the previous
+// column's plane.  Same products, same order of summation as the column-by-column walk: bit-identical outputs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -131,172 +138,251 @@ __device__ __forceinline__ void body(const drc_s16conv_params& p, char* lds, int
     const unsigned cols_unit = (unsigned)n_yt * n_xt;
     const float relu_lo = p.relu ? 0.f : -65504.f;
 
-    for (unsigned it = 0;; ++it) {
+    // ---- the columns of this workgroup, in order (XCD-aware, as in convs16.hip).  The pipeline runs through them WITHOUT draining at a
+    // column's end: ONE flat sequence of steps (column, input plane zi), one cold start before the first, one drain step after the last.
+    // Three cursors walk it: the slabs (RING - 1 steps ahead), the residual requests (one step ahead) and the MFMA / epilogue step itself.
+    struct Col { unsigned n; int y0, x0; bool valid; };
+    auto col_of = [&](unsigned it) __attribute__((always_inline)) {
         const unsigned j = it * per_xcd + qx;
         const unsigned nl = j / cols_unit;
-        const unsigned n = nl * 8 + xcd;
-        if (n >= (unsigned)p.N) break;
         const unsigned rem = j - nl * cols_unit;
         const int yb = (int)(rem / n_xt), xt = (int)(rem - (unsigned)yb * n_xt);
-        const int y0 = yb * RT, x0 = xt * WT;                    // input tile origin
+        Col c;
+        c.n = nl * 8 + xcd;
+        c.valid = c.n < (unsigned)p.N;
+        c.y0 = yb * RT;                                          // input tile origin
+        c.x0 = xt * WT;
+        return c;
+    };
+    // output side of a column: the unit's bases (buffer resources are made from them where they are used) and this lane's even-corner output
+    // voxel (2 yl, 2 (x0 + xl)), chunk (s = 0, g), hi, in output plane 0 (padded + 1).  Past the last column: valid = ok = false (all dropped)
+    struct Ctx { char* yb; const char* rb; unsigned o_lane; bool ok, valid; };
+    auto ctx_of = [&](const Col& c) __attribute__((always_inline)) {
+        Ctx q;
+        const long ub = (long)(c.valid ? c.n : 0u) * o_nB + (long)ct * o_cbB;
+        q.yb = (char*)p.y16 + ub;
+        q.rb = p.res ? (const char*)p.res + ub : (const char*)p.w;
+        const int yl = c.y0 + rl;
+        q.valid = c.valid;
+        q.ok = c.valid && tln.ok && yl < Hi && c.x0 + xl < Wi;
+        q.o_lane = (unsigned)(o_planeB + (long)(2 * yl + 1) * o_rowB + (long)g * o_chunkB + (long)(2 * (c.x0 + xl) + 1) * 16);
+        return q;
+    };
+    auto pick = [](bool s, const Ctx& a, const Ctx& b) __attribute__((always_inline)) {
+        Ctx q;
+        q.yb = s ? a.yb : b.yb;
+        q.rb = s ? a.rb : b.rb;
+        q.o_lane = s ? a.o_lane : b.o_lane;
+        q.ok = s ? a.ok : b.ok;
+        q.valid = s ? a.valid : b.valid;
+        return q;
+    };
+    const unsigned nres = p.res ? 0x7FFFFF00u : 0u;
 
-        // staged rows start at input row y0 = padded row y0 + 1, columns at padded column x0 + 1
-        const char* xcol = (const char*)p.x + (long)n * i_nB + (long)(y0 + 1) * i_rowB + (long)(x0 + 1) * 16;
-        auto stage = [&](int plane, int slot) __attribute__((always_inline)) {
-            const int pl = plane < Di ? plane : Di - 1;
-            char* dst = ring + slot * SLAB;
+    unsigned it_c = 0;                                           // the step's column
+    {
+        const Col c0 = col_of(0);
+        if (!c0.valid) {
+            og.flush(p.ovf);
+            return;
+        }
+    }
+    Ctx cur = ctx_of(col_of(0)), nxt = ctx_of(col_of(1)), prev = cur;
+    prev.ok = prev.valid = false;
+    int zi = 0;                                                  // ... and its input plane
+
+    // ---- slab cursor: staged rows start at input row y0 = padded row y0 + 1, columns at padded column x0 + 1.  stage_next() issues the
+    // slab of the cursor's (column, plane) and moves on through the flat sequence -- into the next column at a column's end; past the
+    // last column it stays on the last slab (re-loaded into a slot nobody reads: the count of vector-memory instructions per step is fixed)
+    auto xcol_of = [&](const Col& c) __attribute__((always_inline)) {
+        return (const char*)p.x + (long)c.n * i_nB + (long)(c.y0 + 1) * i_rowB + (long)(c.x0 + 1) * 16;
+    };
+    unsigned it_s = 0;
+    int pl_s = 0;
+    const char* xcol_s = xcol_of(col_of(0));
+    auto stage_next = [&](int slot) __attribute__((always_inline)) {
+        char* dst = ring + slot * SLAB;
 #pragma unroll
-            for (int ci = 0; ci < NL; ++ci) {
-                const int cc = ci * 4 + wave;
-                const char* src = xcol + (long)(cc >> 3) * i_cbB + (long)(pl + 1) * i_planeB + (long)(cc & 7) * (Wpi * 16);
-                __builtin_amdgcn_global_load_lds(GLOBAL_PTR(src + srcoff), LDS_PTR(dst + cc * CPB), 16, 0, 0);
+        for (int ci = 0; ci < NL; ++ci) {
+            const int cc = ci * 4 + wave;
+            const char* src = xcol_s + (long)(cc >> 3) * i_cbB + (long)(pl_s + 1) * i_planeB + (long)(cc & 7) * (Wpi * 16);
+            __builtin_amdgcn_global_load_lds(GLOBAL_PTR(src + srcoff), LDS_PTR(dst + cc * CPB), 16, 0, 0);
+        }
+        if (pl_s + 1 < Di) {
+            ++pl_s;
+        } else {
+            const Col c = col_of(it_s + 1);
+            if (c.valid) {
+                ++it_s;
+                pl_s = 0;
+                xcol_s = xcol_of(c);
             }
-        };
-        const __amdgpu_buffer_rsrc_t y16r = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)p.y16 + (long)n * o_nB + (long)ct * o_cbB), 0, 0x7FFFFF00, 0x00020000);
-        const __amdgpu_buffer_rsrc_t resr = __builtin_amdgcn_make_buffer_rsrc(p.res ? (void*)((const char*)p.res + (long)n * o_nB + (long)ct * o_cbB) : (void*)p.w, 0,
-                                                                              p.res ? 0x7FFFFF00 : 0, 0x00020000);
-        const int yl = y0 + rl;
-        const bool lane_ok = tln.ok && yl < Hi && x0 + xl < Wi;
-        // this lane's even-corner output voxel (2 yl, 2 (x0 + xl)), chunk (s = 0, g), hi, in output plane 0 (padded + 1)
-        const unsigned o_lane = (unsigned)(o_planeB + (long)(2 * yl + 1) * o_rowB + (long)g * o_chunkB + (long)(2 * (x0 + xl) + 1) * 16);
+        }
+    };
 
-        f32x16 acc[3][2];
+    f32x16 acc[3][2];
 #pragma unroll
-        for (int a = 0; a < 3; ++a)
+    for (int a = 0; a < 3; ++a)
 #pragma unroll
-            for (int b = 0; b < 2; ++b)
+        for (int b = 0; b < 2; ++b)
 #pragma unroll
-                for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+            for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
 
-        // residual tiles are requested ONE STEP before their use (two register sets by the step's parity): output offsets of the planes a
-        // step at input plane zi finishes -- pz = 0 classes: 2 zi; pz = 1 classes: 2 zi - 1 -- and the 4 NF loads
-        u32x4 resv[2][NF][4];
-        auto offsets_of = [&](int zi, bool compute, unsigned (&fo)[NF]) __attribute__((always_inline)) {
+    // residual tiles are requested ONE STEP before their use (two register sets by the parity of the FLAT step index).  A step at input
+    // plane zi finishes output plane 2 zi of its column (pz = 0 classes, context A) and closes 2 zi - 1 (pz = 1 classes, context B) --
+    // at zi = 0 that is the LAST odd plane 2 Di - 1 of the PREVIOUS column: B = that column, its bases, its lanes
+    u32x4 resv[2][NF][4];
+    auto offsets_of = [&](const Ctx& A, int zoA, const Ctx& B, int zoB, unsigned (&fo)[NF]) __attribute__((always_inline)) {
 #pragma unroll
-            for (int ci = 0; ci < NF; ++ci) {
-                const int c = R.cls[ci], pz = c >> 2, py = (c >> 1) & 1, px = c & 1;
-                const int zo = pz ? 2 * zi - 1 : 2 * zi;
-                const bool ok = lane_ok && zo >= 0 && zo < 2 * Di && (compute || pz);
-                fo[ci] = ok ? o_lane + (unsigned)((long)zo * o_planeB + (long)py * o_rowB + px * 16) : 0x80000000u;
-            }
-        };
-        auto request = [&](int zi, auto ST) __attribute__((always_inline)) {        // the residual tiles of the step at input plane zi -> set ST
-            constexpr int S_ = decltype(ST)::value;
-            unsigned fo[NF];
-            offsets_of(zi, zi < Di, fo);
+        for (int ci = 0; ci < NF; ++ci) {
+            const int c = R.cls[ci], pz = c >> 2, py = (c >> 1) & 1, px = c & 1;
+            const bool ok = pz ? B.ok : A.ok;
+            const unsigned ol = pz ? B.o_lane : A.o_lane;
+            const int zo = pz ? zoB : zoA;
+            fo[ci] = ok ? ol + (unsigned)((long)zo * o_planeB + (long)py * o_rowB + px * 16) : 0x80000000u;
+        }
+    };
+    auto request = [&](const Ctx& A, int zoA, const Ctx& B, int zoB, auto ST) __attribute__((always_inline)) {        // -> set ST
+        constexpr int S_ = decltype(ST)::value;
+        unsigned fo[NF];
+        offsets_of(A, zoA, B, zoB, fo);
+        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)A.rb, 0, nres, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)B.rb, 0, nres, 0x00020000);
 #pragma unroll
-            for (int ci = 0; ci < NF; ++ci)
+        for (int ci = 0; ci < NF; ++ci)
 #pragma unroll
-                for (int q = 0; q < 4; ++q)      // q: (lo?, s): chunks s*2 (+g in o_lane), + 4 for lo
-                    resv[S_][ci][q] = __builtin_amdgcn_raw_buffer_load_b128(resr, fo[ci] + (unsigned)(((q >> 1) * 4 + (q & 1) * 2) * o_chunkB), 0, 0);
-        };
+            for (int q = 0; q < 4; ++q)      // q: (lo?, s): chunks s*2 (+g in o_lane), + 4 for lo
+                resv[S_][ci][q] = __builtin_amdgcn_raw_buffer_load_b128((R.cls[ci] >> 2) ? rb : ra, fo[ci] + (unsigned)(((q >> 1) * 4 + (q & 1) * 2) * o_chunkB), 0, 0);
+    };
+    // ---- the one cold start
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(S16_WAITCNT(63, 0));
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    request(cur, 0, prev, 0, std::integral_constant<int, 0>{});
+#pragma unroll
+    for (int s_ = 0; s_ + 1 < RING; ++s_) stage_next(s_);
+    __builtin_amdgcn_s_waitcnt(S16_WAITCNT((RING - 2) * NL, 15));      // plane 0 landed (step 0's own wait counts a previous step's stores)
+    int slot = 0;
+
+    // one step of parity P (of the flat step index): input plane zi of column `cur` (COMPUTE); COMPUTE = false: the drain step after the
+    // last column (`cur` is past the end: it only closes the last odd output plane of `prev`)
+    auto step = [&](auto PT, auto COMPT) __attribute__((always_inline)) {
+        constexpr int P = decltype(PT)::value;
+        constexpr bool COMPUTE = decltype(COMPT)::value;
         asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(S16_WAITCNT(63, 0));
+        __builtin_amdgcn_s_waitcnt(S16_WAITCNT((RING - 2) * NL + NS, 0));
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        request(0, std::integral_constant<int, 0>{});
+        const bool first = zi == 0, last = zi + 1 == Di;
+        // output planes finished in this step (their residual tiles were requested one step ago into set P); the next step's go out now
+        const Ctx cB = pick(first, prev, cur);
+        unsigned fo[NF];
+        offsets_of(cur, 2 * zi, cB, first ? 2 * Di - 1 : 2 * zi - 1, fo);
+        request(pick(last, nxt, cur), last ? 0 : 2 * zi + 2, cur, 2 * zi + 1, std::integral_constant<int, P ^ 1>{});
+        {
+            int ns = slot + RING - 1; ns = ns >= RING ? ns - RING : ns;
+            stage_next(ns);
+        }
+        const __amdgpu_buffer_rsrc_t ya = __builtin_amdgcn_make_buffer_rsrc((void*)cur.yb, 0, 0x7FFFFF00, 0x00020000);
+        const __amdgpu_buffer_rsrc_t yb_ = __builtin_amdgcn_make_buffer_rsrc((void*)cB.yb, 0, 0x7FFFFF00, 0x00020000);
+        const __attribute__((address_space(3))) char* sb = ringl + slot * SLAB + bbase;
+        auto run_tap = [&](int t) __attribute__((always_inline)) {
+            const UTap u = TL.t[t];
+            const int pz = R.cls[u.ci] >> 2;
+            const int ai = pz ? (u.open ? (P ^ 1) : P) : 0;
 #pragma unroll
-        for (int s_ = 0; s_ + 1 < RING; ++s_) stage(s_, s_);
-        __builtin_amdgcn_s_waitcnt(S16_WAITCNT((RING - 2) * NL, 15));      // plane 0 landed (step 0's own wait counts a previous step's stores)
-        int slot = 0;
-
-        // one input plane zi (COMPUTE) of parity P; COMPUTE = false: the drain step (closes the last odd output plane)
-        auto step = [&](int zi, auto PT, auto COMPT) __attribute__((always_inline)) {
-            constexpr int P = decltype(PT)::value;
-            constexpr bool COMPUTE = decltype(COMPT)::value;
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_waitcnt(S16_WAITCNT((RING - 2) * NL + NS, 0));
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            // output planes finished in this step (their residual tiles were requested one step ago into set P); the next step's go out now
-            unsigned fo[NF];
-            offsets_of(zi, COMPUTE, fo);
-            request(zi + 1, std::integral_constant<int, P ^ 1>{});
-            {
-                int ns = slot + RING - 1; ns = ns >= RING ? ns - RING : ns;
-                stage(zi + RING - 1, ns);
+            for (int kk = 0; kk < 4; ++kk) {
+                const int off = ((kk >> 1) * 8 + (kk & 1) * 2) * CPB + (u.sy * SXI + u.sx) * 16;
+                const f16x8 h_ = *(lds_frag*)(sb + off), l_ = *(lds_frag*)(sb + off + 4 * CPB);
+                acc[u.ci][ai] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[t][kk], h_, acc[u.ci][ai], 0, 0, 0);
+                acc[u.ci][ai] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[t][kk], l_, acc[u.ci][ai], 0, 0, 0);
+                acc[u.ci][ai] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[t][kk], h_, acc[u.ci][ai], 0, 0, 0);
             }
-            const __attribute__((address_space(3))) char* sb = ringl + slot * SLAB + bbase;
-            auto run_tap = [&](int t) __attribute__((always_inline)) {
-                constexpr int dummy = 0; (void)dummy;
-                const UTap u = TL.t[t];
-                const int pz = R.cls[u.ci] >> 2;
-                const int ai = pz ? (u.open ? (P ^ 1) : P) : 0;
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    const int off = ((kk >> 1) * 8 + (kk & 1) * 2) * CPB + (u.sy * SXI + u.sx) * 16;
-                    const f16x8 h_ = *(lds_frag*)(sb + off), l_ = *(lds_frag*)(sb + off + 4 * CPB);
-                    acc[u.ci][ai] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[t][kk], h_, acc[u.ci][ai], 0, 0, 0);
-                    acc[u.ci][ai] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[t][kk], l_, acc[u.ci][ai], 0, 0, 0);
-                    acc[u.ci][ai] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[t][kk], h_, acc[u.ci][ai], 0, 0, 0);
-                }
-            };
-            if constexpr (COMPUTE) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    if (!TL.t[t].open) run_tap(t);
-            }
-            // this step's residual tiles were requested at the head of the PREVIOUS step: younger are that step's DMAs and stores and this step's
-            // requests and DMAs
-            __builtin_amdgcn_s_waitcnt(S16_WAITCNT(2 * NL + 2 * NS, 15));
-            __builtin_amdgcn_sched_barrier(0);
-            // ---- epilogues of the finished accumulators (in the shadow of the opening taps below)
-#pragma unroll
-            for (int ci = 0; ci < NF; ++ci) {
-                const int pz = R.cls[ci] >> 2;
-                const int ai = pz ? P : 0;
-                const f32x16 a = acc[ci][ai];
-                const unsigned long long og_keep = S16Ovf::lanes(fo[ci] != 0x80000000u);      // dropped lanes / planes hold over-read data
-                f16x8 hi[2], lo[2];
-                float og_mx = 0.f;                                   // largest |stored value| of this accumulator (one compare per accumulator)
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const f32x4 sc0 = *(lds_f4*)(bnl + g * 32 + s * 8), sc1 = *(lds_f4*)(bnl + g * 32 + s * 8 + 4);
-                    const f32x4 sh0 = *(lds_f4*)(bnl + g * 32 + 16 + s * 8), sh1 = *(lds_f4*)(bnl + g * 32 + 16 + s * 8 + 4);
-                    const f16x8 rh = __builtin_bit_cast(f16x8, resv[P][ci][s]), rl_ = __builtin_bit_cast(f16x8, resv[P][ci][2 + s]);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float sc_ = e < 4 ? sc0[e & 3] : sc1[e & 3], sh_ = e < 4 ? sh0[e & 3] : sh1[e & 3];
-                        float x_ = a[s * 8 + e] * sc_ + sh_;
-                        x_ += (float)rh[e] + (float)rl_[e];
-                        x_ = __builtin_amdgcn_fmed3f(x_, relu_lo, 65504.f);
-                        og_mx = fmaxf(og_mx, __builtin_fabsf(x_));
-                        hi[s][e] = (_Float16)x_;
-                        lo[s][e] = (_Float16)(x_ - (float)hi[s][e]);
-                    }
-                }
-                og.see_max(og_mx, og_keep);
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi[s]), y16r, fo[ci] + (unsigned)((s * 2) * o_chunkB), 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo[s]), y16r, fo[ci] + (unsigned)((4 + s * 2) * o_chunkB), 0, 0);
-                }
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[ci][ai][e] = 0.f;
-            }
-            if constexpr (COMPUTE) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    if (TL.t[t].open) run_tap(t);
-            }
-            slot = slot + 1 == RING ? 0 : slot + 1;
         };
-        using F = std::false_type;
-        using T = std::true_type;
-        using I0 = std::integral_constant<int, 0>;
-        using I1 = std::integral_constant<int, 1>;
-        int zi = 0;
-#pragma unroll 1
-        for (; zi + 1 < Di; zi += 2) {
-            step(zi, I0{}, T{});
-            step(zi + 1, I1{}, T{});
+        if constexpr (COMPUTE) {
+            // the completing taps.  kd = 0 at zi = 0 would feed output plane -1: not run -- acc[.][P] holds the previous column's last odd
+            // plane there (opened by its last step's kd = 2 taps; the kd = 0 taps of that plane read the zero halo: nothing to add)
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+                if (!TL.t[t].open && !(R.cls[TL.t[t].ci] >> 2)) run_tap(t);
+            if (!first) {
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+                    if (!TL.t[t].open && (R.cls[TL.t[t].ci] >> 2)) run_tap(t);
+            }
         }
-        if (zi < Di) {
-            step(zi, I0{}, T{});
-            step(zi + 1, I1{}, F{});
+        // this step's residual tiles were requested at the head of the PREVIOUS step: younger are that step's DMAs and stores and this step's
+        // requests and DMAs
+        __builtin_amdgcn_s_waitcnt(S16_WAITCNT(2 * NL + 2 * NS, 15));
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- epilogues of the finished accumulators (in the shadow of the opening taps below)
+#pragma unroll
+        for (int ci = 0; ci < NF; ++ci) {
+            const int pz = R.cls[ci] >> 2;
+            const int ai = pz ? P : 0;
+            const f32x16 a = acc[ci][ai];
+            const unsigned long long og_keep = S16Ovf::lanes(fo[ci] != 0x80000000u);      // dropped lanes / planes hold over-read data
+            f16x8 hi[2], lo[2];
+            float og_mx = 0.f;                                   // largest |stored value| of this accumulator (one compare per accumulator)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const f32x4 sc0 = *(lds_f4*)(bnl + g * 32 + s * 8), sc1 = *(lds_f4*)(bnl + g * 32 + s * 8 + 4);
+                const f32x4 sh0 = *(lds_f4*)(bnl + g * 32 + 16 + s * 8), sh1 = *(lds_f4*)(bnl + g * 32 + 16 + s * 8 + 4);
+                const f16x8 rh = __builtin_bit_cast(f16x8, resv[P][ci][s]), rl_ = __builtin_bit_cast(f16x8, resv[P][ci][2 + s]);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float sc_ = e < 4 ? sc0[e & 3] : sc1[e & 3], sh_ = e < 4 ? sh0[e & 3] : sh1[e & 3];
+                    float x_ = a[s * 8 + e] * sc_ + sh_;
+                    x_ += (float)rh[e] + (float)rl_[e];
+                    x_ = __builtin_amdgcn_fmed3f(x_, relu_lo, 65504.f);
+                    og_mx = fmaxf(og_mx, __builtin_fabsf(x_));
+                    hi[s][e] = (_Float16)x_;
+                    lo[s][e] = (_Float16)(x_ - (float)hi[s][e]);
+                }
+            }
+            og.see_max(og_mx, og_keep);
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi[s]), pz ? yb_ : ya, fo[ci] + (unsigned)((s * 2) * o_chunkB), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo[s]), pz ? yb_ : ya, fo[ci] + (unsigned)((4 + s * 2) * o_chunkB), 0, 0);
+            }
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[ci][ai][e] = 0.f;
+        }
+        if constexpr (COMPUTE) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+                if (TL.t[t].open) run_tap(t);
+        }
+        slot = slot + 1 == RING ? 0 : slot + 1;
+        // on to the next step of the flat sequence
+        if (last) {
+            zi = 0;
+            prev = cur;
+            cur = nxt;
+            ++it_c;
+            nxt = ctx_of(col_of(it_c + 1));
         } else {
-            step(zi, I0{}, F{});
+            ++zi;
         }
+    };
+    using F = std::false_type;
+    using T = std::true_type;
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+#pragma unroll 1
+    for (;;) {
+        if (!cur.valid) {
+            step(I0{}, F{});
+            break;
+        }
+        step(I0{}, T{});
+        if (!cur.valid) {
+            step(I1{}, F{});
+            break;
+        }
+        step(I1{}, T{});
     }
     og.flush(p.ovf);
 }
