@@ -1,0 +1,113 @@
+"""PointRCNN: the 3D stage of Disp R-CNN (reference: point_rcnn/lib/net/point_rcnn.py), evaluation forward (`_forward_val`) on HIP.
+
+2D results with per-ROI disparities and masks -> remove_empty_proposals -> InstancePointCloud (modeling/pointcloud.py) -> RPN ->
+the RPN's clouds and proposals moved back to the camera frame (un-centred, rotated back; the proposals through their corners, as the
+reference does) -> RCNNNet.refine -> the fields `box3d` ('ry_lhwxyz'), `scores_3d` and `random` on the left results, one box per
+instance.  Without an instance the fields are empty (`random` too, which the reference omits there); with RCNN.ENABLED = False the best RPN proposal of each instance is returned
+(`box3d` in 'xyzhwl_ry', `scores_3d`).  The reference writes that branch's fields to the first image only; here they are split over
+the images as the RCNN branch's are, which is the same for its one-image batches.
+
+The plumbing between the networks is plain torch on the device.  From the RPN's output to the end of `refine` nothing reads the
+device; the fields are then brought to the host in one copy (the reference's fields are CPU tensors too).
+
+The state-dict keys are the reference's (`rpn.*`, `rcnn_net.*`).  No training forward.
+"""
+import torch
+import torch.nn as nn
+
+from disprcnn_amd.layers.rpn_proposals import points_depth
+from disprcnn_amd.modeling.pointcloud import InstancePointCloud
+from disprcnn_amd.structures.bounding_box_3d import Box3DList
+
+from .rcnn_net import RCNNNet
+from .rpn import RPN
+
+
+def remove_empty_proposals(left_results, right_results):
+    """Drop the pairs whose left or right box is not more than a pixel wide and high."""
+    ret_left, ret_right = [], []
+    for lr, rr in zip(left_results, right_results):
+        keep = (lr.bbox[:, 2] > lr.bbox[:, 0] + 1) & (lr.bbox[:, 3] > lr.bbox[:, 1] + 1) & \
+               (rr.bbox[:, 2] > rr.bbox[:, 0] + 1) & (rr.bbox[:, 3] > rr.bbox[:, 1] + 1)
+        ret_left.append(lr[keep])
+        ret_right.append(rr[keep])
+    return ret_left, ret_right
+
+
+def _attach(left_results, fields):
+    """fields: {name: (R, ...) tensor over all instances} -> split over the images in order"""
+    counts = [len(a) for a in left_results]
+    for name, (value, wrap) in fields.items():
+        for lr, v in zip(left_results, torch.split(value, counts)):
+            lr.add_field(name, wrap(v, lr) if wrap else v)
+    return left_results
+
+
+def combine_2d_3d(left_results, box, score, random):
+    """box (R,7) 'ry_lhwxyz', score (R), random (R) of every instance in order -> fields on the left results (CPU tensors)."""
+    box, score, random = box.cpu(), score.cpu(), random.cpu()
+    return _attach(left_results, {"box3d": (box, lambda v, lr: Box3DList(v, size=lr.size, mode="ry_lhwxyz")),
+                                  "scores_3d": (score, None), "random": (random, None)})
+
+
+class PointRCNN(nn.Module):
+    def __init__(self, cfg):
+        super().__init__()
+        self.total_cfg = cfg
+        self.cfg = cfg.MODEL.POINTRCNN
+        if not self.cfg.RPN.ENABLED:
+            raise NotImplementedError("PointRCNN without its RPN: the RCNN stage reads the RPN's outputs")
+        self.rpn = RPN(self.cfg, self.total_cfg)
+        if self.cfg.RCNN.ENABLED:
+            self.rcnn_net = RCNNNet(self.cfg, self.total_cfg)
+        self.pointcloud = InstancePointCloud(npoints=self.cfg.RPN.NPOINTS, mask_threshold=0.5, mask_padding=1)    # _forward_val's Masker
+
+    def proposals_to_camera(self, rpn_proposals, pts_mean, rot_angle):
+        """The RPN's dict in the centred, rotated frame of its clouds -> the same dict in the camera frame (point_rcnn.py:296-312)."""
+        back = lambda p: InstancePointCloud.rotate_back(p + pts_mean[:, None, :], rot_angle)
+        out = dict(rpn_proposals)
+        out["backbone_xyz"] = back(rpn_proposals["backbone_xyz"])
+        out["pts_depth"] = points_depth(out["backbone_xyz"])
+        out["rpn_xyz"] = back(rpn_proposals["rpn_xyz"])
+        B = pts_mean.shape[0]
+        corners = Box3DList(rpn_proposals["roi_boxes3d"].reshape(-1, 7), (1, 1), "xyzhwl_ry").convert("corners").bbox_3d
+        out["roi_boxes3d"] = Box3DList(back(corners.view(B, -1, 3)).contiguous(), (1, 1), "corners").convert("xyzhwl_ry").bbox_3d.view(B, -1, 7)
+        return out
+
+    def _forward_val(self, left_results, right_results, targets):
+        if targets is None:
+            raise ValueError("PointRCNN: the evaluation forward needs `targets`: one BoxList with a 'calib' field (or one calibration) per image")
+        left_results, right_results = remove_empty_proposals(left_results, right_results)
+        calibs = [t.get_field("calib") if hasattr(t, "get_field") else t for t in targets]
+        pts_input, pts_mean, rot_angle = self.pointcloud(left_results, right_results, calibs)
+        if pts_input.numel() == 0:
+            for lr in left_results:
+                lr.add_field("box3d", Box3DList(torch.empty((0, 7)), size=lr.size, mode="ry_lhwxyz"))
+                lr.add_field("scores_3d", torch.empty((0,)))
+                if hasattr(self, "rcnn_net"):                      # the reference leaves this one out; consumers of the RCNN branch read it
+                    lr.add_field("random", torch.empty((0,), dtype=torch.int64))
+            return left_results, right_results, {}
+        with torch.no_grad():
+            rpn_proposals, _ = self.rpn(pts_input)
+            if hasattr(self, "rcnn_net"):
+                box, score, random = self.rcnn_net.refine(self.proposals_to_camera(rpn_proposals, pts_mean, rot_angle))
+                left_results = combine_2d_3d(left_results, box, score, random)
+            else:
+                box3d = rpn_proposals["roi_boxes3d"].clone()
+                B = box3d.shape[0]
+                box3d[:, :, 0:3] = box3d[:, :, 0:3] + pts_mean[:, None, :]
+                corners = Box3DList(box3d.reshape(-1, 7), (1, 1), "xyzhwl_ry").convert("corners").bbox_3d.view(B, -1, 3)
+                corners = InstancePointCloud.rotate_back(corners, rot_angle).view(B, -1, 24)
+                score_3d = rpn_proposals["roi_scores_raw"]
+                idx = score_3d.argmax(dim=1)
+                best = torch.gather(corners, 1, idx.view(B, 1, 1).expand(B, 1, 24))[:, 0]
+                boxes = Box3DList(best, (1, 1), "corners").convert("xyzhwl_ry").bbox_3d
+                scores = torch.gather(score_3d, 1, idx.view(B, 1))[:, 0].cpu()
+                left_results = _attach(left_results, {"box3d": (boxes, lambda v, lr: Box3DList(v, (1, 1), "xyzhwl_ry")),
+                                                      "scores_3d": (scores, None)})
+        return left_results, right_results, {}
+
+    def forward(self, left_inputs, right_inputs, targets=None):
+        if self.training:
+            raise NotImplementedError("PointRCNN: only the evaluation forward is implemented (no loss, no backward); call .eval()")
+        return self._forward_val(left_inputs, right_inputs, targets)

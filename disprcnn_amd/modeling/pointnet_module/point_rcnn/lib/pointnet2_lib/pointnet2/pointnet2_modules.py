@@ -2,7 +2,9 @@
 only, on the HIP kernels: the index ops of layers/pointnet2.py and the fused shared MLPs of layers/pn2_mlp.py.
 
 An SA module is FPS -> gather -> per scale: ball query -> one fused group / MLP / max kernel that writes its scale's channels into
-the module's output, so neither the grouped tensor nor a torch.cat exists.  An FP module is three_nn -> weights -> three_interpolate
+the module's output, so neither the grouped tensor nor a torch.cat exists.  With npoint=None (GroupAll, the RCNN's last level) the one
+neighbourhood is the whole cloud: the same kernel with new_xyz = 0 (x - 0 is exact, so the raw coordinates are fed as GroupAll does),
+M = 1 and idx = 0..N-1; the cloud must fit one neighbourhood (N <= 64).  An FP module is three_nn -> weights -> three_interpolate
 -> the MLP, whose first layer reads the interpolated and the skip features as two inputs.  FPS and ball query read coordinates only,
 so every index equals the reference's.
 """
@@ -29,14 +31,13 @@ class PointnetSAModuleMSG(nn.Module):
             raise NotImplementedError("instance_norm is not supported by the HIP shared-MLP kernels")
         if not use_xyz:
             raise NotImplementedError("use_xyz=False: the fused kernel always feeds the relative coordinates")
-        if npoint is None:
-            raise NotImplementedError("npoint=None (GroupAll) is not supported by the fused kernel")
         self.npoint = npoint
         self.pool_method = pool_method
         self.groupers = nn.ModuleList()
         self.mlps = nn.ModuleList()
         for radius, nsample, spec in zip(radii, nsamples, mlps):
-            self.groupers.append(pointnet2_utils.QueryAndGroup(radius, nsample, use_xyz=use_xyz))
+            self.groupers.append(pointnet2_utils.QueryAndGroup(radius, nsample, use_xyz=use_xyz) if npoint is not None
+                                 else pointnet2_utils.GroupAll(use_xyz))
             spec = list(spec)
             spec[0] += 3
             self.mlps.append(pt_utils.SharedMLP(spec, bn=bn, instance_norm=instance_norm))
@@ -45,6 +46,8 @@ class PointnetSAModuleMSG(nn.Module):
         """xyz (B,N,3), features (B,C,N) or None -> new_xyz (B,npoint,3), new_features (B, sum of the scales' widths, npoint)."""
         if self.training:
             raise NotImplementedError("PointnetSAModuleMSG: the HIP forward is inference only; call .eval()")
+        if self.npoint is None:
+            return None, self._forward_group_all(xyz, features)
         with torch.no_grad():
             if new_xyz is None:
                 fps_idx = pointnet2_utils.furthest_point_sample(xyz, self.npoint)
@@ -57,6 +60,26 @@ class PointnetSAModuleMSG(nn.Module):
                 pn2_mlp.sa_mlp_max(xyz, new_xyz, features, idx, layers, out=out, c_off=c_off)
                 c_off += layers[-1].cout
         return new_xyz, out
+
+    def _forward_group_all(self, xyz, features):
+        """GroupAll: (B,N,3), (B,C,N) -> (B, sum of the widths, 1), the max over all N points of the MLP of raw xyz ++ features."""
+        B, N = xyz.shape[0], xyz.shape[1]
+        if not 1 <= N <= 64:
+            raise NotImplementedError(f"PointnetSAModuleMSG with npoint=None: the fused kernel holds one neighbourhood of at most 64 points, "
+                                      f"got {N}")
+        with torch.no_grad():
+            folded = [m.folded() for m in self.mlps]
+            out = torch.empty((B, sum(f[-1].cout for f in folded), 1), dtype=torch.float32, device=xyz.device)
+            key = (B, N, xyz.device)
+            if getattr(self, "_group_all", (None,))[0] != key:      # constants of the shape: made once, not per call
+                self._group_all = (key, torch.zeros((B, 1, 3), dtype=torch.float32, device=xyz.device),
+                                   torch.arange(N, dtype=torch.int32, device=xyz.device).view(1, 1, N).expand(B, 1, N).contiguous())
+            _, origin, idx = self._group_all
+            c_off = 0
+            for layers in folded:
+                pn2_mlp.sa_mlp_max(xyz, origin, features, idx, layers, out=out, c_off=c_off)
+                c_off += layers[-1].cout
+        return out
 
 
 class PointnetSAModule(PointnetSAModuleMSG):

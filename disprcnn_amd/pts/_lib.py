@@ -37,6 +37,8 @@ _SIGS = {
     "drc_pn2_pointwise_mlp_fwd": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _I, _I, _P]),
     "drc_rpn_points_depth": (_I, [_L, _P, _P, _P]),
     "drc_rpn_decode_proposals": (_I, [_L, _I, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
+    "drc_rcnn_pool_canonical_fwd": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _F, _F, _P, _P, _P, _P, _P]),
+    "drc_rcnn_decode_boxes": (_I, [_L, _I, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/disprcnn_pts.h"
+#include "box3d_pt.h"
 
 namespace {
 
@@ -28,9 +29,9 @@ constexpr float kMargin = 1e-5f;            // check_in_box2d MARGIN
 constexpr int kPoly = 24;                   // 16 edge intersections + 8 corners
 constexpr int kWalkSlots = 8;               // removal words per lane in the walk
 constexpr int kMaxNmsBoxes = 64 * 64 * kWalkSlots;
-constexpr int kPoolThreads = 256;
-constexpr int kMaxPoolSamples = 8192;       // LDS index list of roipool3d: 32 KB
-constexpr float kMaxDis = 10.0f;            // roipool3dLauncher's max_dis
+using box3d_pt::kMaxPoolSamples;
+using box3d_pt::kPoolThreads;
+using box3d_pt::pt_in_box3d;                // shared with rcnn_ops.hip
 
 // One box [x1, y1, x2, y2, ry], everything box_overlap / check_in_box2d / iou_bev derive from it alone.
 struct BoxG {
@@ -306,18 +307,7 @@ __global__ __launch_bounds__(64) void nms_walk_kernel(int Nmax, int cw, const in
     if (lane == 0) num_keep[b] = kept;
 }
 
-// ---- roipool3d
-// pt_in_box3d with its mixed precision: h / 2.0, l / 2.0, w / 2.0 are double; cos / sin of the float angle (cosa, sina)
-__device__ __forceinline__ bool pt_in_box3d(float x, float y, float z, const float* bx, float cosa, float sina) {
-    const float cx = bx[0], bottom_y = bx[1], cz = bx[2], h = bx[3], w = bx[4], l = bx[5];
-    const float cy = (float)((double)bottom_y - (double)h / 2.0);
-    if (fabsf(x - cx) > kMaxDis || (double)fabsf(y - cy) > (double)h / 2.0 || fabsf(z - cz) > kMaxDis) return false;
-    const float x_rot = (x - cx) * cosa + (z - cz) * (-sina);
-    const float z_rot = (x - cx) * sina + (z - cz) * cosa;
-    return ((double)x_rot >= (double)(-l) / 2.0) & ((double)x_rot <= (double)l / 2.0) & ((double)z_rot >= (double)(-w) / 2.0) &
-           ((double)z_rot <= (double)w / 2.0);
-}
-
+// ---- roipool3d (pt_in_box3d and the selection of the first S in-box points: box3d_pt.h)
 __global__ __launch_bounds__(kPoolThreads) void roipool3d_kernel(int N, int M, int C, int S, const float* __restrict__ xyz,
                                                                  const float* __restrict__ boxes3d, const float* __restrict__ feat,
                                                                  float* __restrict__ pooled, int32_t* __restrict__ empty_flag) {
@@ -328,25 +318,7 @@ __global__ __launch_bounds__(kPoolThreads) void roipool3d_kernel(int N, int M, i
     const float* bx = boxes3d + (int64_t)bm * 7;
     const float cosa = cosf(bx[6]), sina = sinf(bx[6]);
     const float* p = xyz + (int64_t)b * N * 3;
-    int cnt = 0;                            // block-uniform
-    for (int base = 0; base < N && cnt < S; base += kPoolThreads) {
-        const int k = base + tid;
-        const bool in = k < N && pt_in_box3d(p[(int64_t)k * 3 + 0], p[(int64_t)k * 3 + 1], p[(int64_t)k * 3 + 2], bx, cosa, sina);
-        const uint64_t bal = __ballot(in);
-        if (lane == 0) wcnt[wave] = __popcll(bal);
-        __syncthreads();
-        int before = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < kPoolThreads / 64; ++w) {
-            const int c = wcnt[w];
-            before += w < wave ? c : 0;
-            tot += c;
-        }
-        const int pos = cnt + before + __popcll(bal & ((1ull << lane) - 1ull));
-        if (in && pos < S) sidx[pos] = k;
-        cnt += tot;
-        __syncthreads();
-    }
+    const int cnt = box3d_pt::select_in_box(N, S, p, bx, cosa, sina, sidx, wcnt);      // block-uniform
     if (cnt == 0) {
         if (tid == 0) empty_flag[bm] = 1;
         return;

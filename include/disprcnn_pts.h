@@ -127,6 +127,32 @@ int drc_rpn_decode_proposals(int64_t n, int R, const float* xyz, const float* re
  * the reference's recordings were made with; bit-identical on every device. */
 int drc_rpn_points_depth(int64_t n, const float* xyz, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * PointRCNN RCNN stage (pts/rcnn_ops.hip; rcnn_net.py's ROI_SAMPLE_JIT eval branch, rcnn_inference.py).
+ * ------------------------------------------------------------------------------------- */
+/* ROI pooling fused with the canonical transform, one workgroup per (cloud, ROI), in the layouts the RPN returns and the shared MLPs
+ * read: rpn_xyz [B,N,3], feat [B,C,N] (channel-major; null when C = 0), seg_mask [B,N], pts_depth [B,N] (read when use_depth != 0),
+ * rois [B,M,7] as [x,y,z,h,w,l,ry] (NOT enlarged: the kernel applies enlarge_box3d with extra_width and extra_width2 = the caller's
+ * fp32 rounding of 2 * extra_width).  For r = b * M + m and E = 1 + (use_depth != 0):
+ *   xyz  [R,S,3]    <- (p - roi centre) rotated about y by roi ry, p = the first S in-box points in index order, repeated cyclically
+ *   pts  [R,3+E,S]  <- canonical x, y, z, seg_mask, pts_depth / 70 - 0.5
+ *   ofeat [R,C,S]   <- feat[b, :, selected]
+ *   empty_flag [R] int32 <- 1 for a ROI without a point: its features are 0 (the depth channel too) and its xyz is rotate(0 - centre).
+ * Every element of every output is written.  In-box test: pt_in_box3d, max_dis 10.  1 <= S <= drc_box3d_max_pool_samples(). */
+int drc_rcnn_pool_canonical_fwd(int B, int N, int M, int C, int S, const float* rpn_xyz, const float* feat, const float* seg_mask,
+                                const float* pts_depth, int use_depth, const float* rois, float extra_width, float extra_width2, float* xyz,
+                                float* pts, float* ofeat, int32_t* empty_flag, void* stream);
+/* decode_bbox_target in the RCNN's form (get_xz_fine = True, get_ry_fine = True, get_y_by_bin = y_by_bin; first-maximum argmax): the
+ * rotation by -roi_ry, ry + roi_ry, the ROI's centre added on x and z (y = roi_y + offset), then boxes3d_to_bev and the sigmoid of the
+ * class logit in the same pass: rois [n,7], reg [n,R], cls [n] -> boxes [n,7], bev [n,5], norm_score [n].
+ * R = 4 * per_loc_bin_num + (y_by_bin ? 2 * loc_y_bin_num : 1) + 2 * num_head_bin + 3.  Constants as drc_rpn_decode_proposals: the
+ * reference's Python doubles rounded to fp32 by the caller (half_bin = loc_bin_size / 2, half_y_bin = loc_y_bin_size / 2,
+ * angle_per_class = (pi / 2) / num_head_bin, half_angle = angle_per_class / 2, quarter_pi = pi / 4). */
+int drc_rcnn_decode_boxes(int64_t n, int R, const float* rois, const float* reg, const float* cls, int per_loc_bin_num, int loc_y_bin_num,
+                          int num_head_bin, int y_by_bin, float loc_bin_size, float half_bin, float loc_scope, float loc_y_bin_size,
+                          float half_y_bin, float loc_y_scope, float angle_per_class, float half_angle, float quarter_pi, float anchor_h,
+                          float anchor_w, float anchor_l, float* boxes, float* bev, float* norm_score, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
