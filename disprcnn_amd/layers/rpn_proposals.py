@@ -3,6 +3,7 @@
     decode_rpn_boxes(xyz, reg, mean_size, loc_scope, loc_bin_size, num_head_bin, xz_fine) -> (boxes7 [B,N,7], bev5 [B,N,5])
     propose(scores, boxes7, bev5, pre_nms_top_n, post_nms_top_n, nms_thresh)               -> (rois [B,post,7], roi_scores [B,post])
     points_depth(xyz)                                                                      -> |p| [B,N]
+    rpn_to_camera(xyz, boxes, mean, rot)                                                   -> (xyz_cam [B,N,3], depth [B,N], boxes_cam [B,M,7])
 
 decode is one kernel (bin argmax, residuals, the angle wrap, y moved to the box bottom, and the BEV form for the NMS), fp32 in the
 reference's expression order, so equal inputs give the reference's bits.  The reference's constants are Python doubles that meet the
@@ -58,6 +59,32 @@ def points_depth(xyz):
         _lib.check(_lib.lib().drc_rpn_points_depth(out.numel(), E._ptr(xyz.contiguous()), E._ptr(out), E._stream_ptr(xyz.device)),
                    "drc_rpn_points_depth")
     return out
+
+
+def rpn_to_camera(xyz, boxes, mean, rot):
+    """The RPN's clouds xyz (B,N,3) and proposals boxes (B,M,7) 'xyzhwl_ry', both in the centred, rotated frame of their instance
+    (mean (B,3) fp32, rot (B) fp64), -> (xyz_cam (B,N,3), depth (B,N), boxes_cam (B,M,7)) in the camera frame.  One kernel: the points are
+    un-centred and rotated back, depth is points_depth of the result (same bits), the boxes go through their corners as Box3DList does."""
+    what = "rpn_to_camera"
+    if not (xyz.is_cuda and boxes.is_cuda and mean.is_cuda and rot.is_cuda):
+        raise RuntimeError(f"{what}: expected CUDA/HIP tensors on an MI355X; the HIP path has no CPU fallback")
+    B = mean.shape[0]
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or boxes.dim() != 3 or boxes.shape[2] != 7 or xyz.shape[0] != B or boxes.shape[0] != B or \
+            mean.shape != (B, 3) or rot.shape != (B,):
+        raise RuntimeError(f"{what}: xyz [B,N,3], boxes [B,M,7], mean [B,3], rot [B] expected, got {tuple(xyz.shape)}, {tuple(boxes.shape)}, "
+                           f"{tuple(mean.shape)}, {tuple(rot.shape)}")
+    if xyz.dtype != torch.float32 or boxes.dtype != torch.float32 or mean.dtype != torch.float32 or rot.dtype != torch.float64:
+        raise RuntimeError(f"{what}: fp32 xyz, boxes and mean and an fp64 rot expected")
+    N, M = xyz.shape[1], boxes.shape[1]
+    dev = xyz.device
+    xyz_cam = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+    depth = torch.empty((B, N), dtype=torch.float32, device=dev)
+    boxes_cam = torch.empty((B, M, 7), dtype=torch.float32, device=dev)
+    if B and (N or M):
+        st = _lib.lib().drc_rpn_to_camera_fwd(B, N, M, E._ptr(xyz.contiguous()), E._ptr(boxes.contiguous()), E._ptr(mean.contiguous()),
+                                              E._ptr(rot.contiguous()), E._ptr(xyz_cam), E._ptr(depth), E._ptr(boxes_cam), E._stream_ptr(dev))
+        _lib.check(st, "drc_rpn_to_camera_fwd")
+    return xyz_cam, depth, boxes_cam
 
 
 def propose(scores, boxes7, bev5, pre_nms_top_n, post_nms_top_n, nms_thresh):

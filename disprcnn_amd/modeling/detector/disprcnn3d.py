@@ -8,8 +8,13 @@ require_mask_tgts, :52-112: Masker paste & ground-truth mask, DisparityMap crop 
 truncation (:223-243) -> PSMNet (train mode, three heads) -> EndPointErrorLoss -> {'disp_loss'}.
 Differences by design: the per-ROI box arithmetic, the crop + normalisation and the whole target preparation are single HIP
 kernels (no ``.tolist()`` host syncs, no Python per-ROI loop, no full-size per-ROI mask images); an empty ROI set yields a
-zero loss that still reaches every parameter, so data-parallel ranks never skip a step.  PointRCNN (DET3D_ON) is
-downstream of the hot path and raises.
+zero loss that still reaches every parameter, so data-parallel ranks never skip a step.
+
+The 3D stage (reference :34-43, :281-282, :317-323).  MODEL.DET3D_ON builds `pcnet = PointRCNN(cfg)` and the evaluation forward hands the
+left / right results and `lr_targets["left"]` (one calibration per image) to it: the left results come back with `box3d`, `scores_3d` (and
+`random` with the RCNN).  MODEL.DISPNET_ON false builds no PSMNet: the incoming left results must then carry `disparity` and `mask`
+already -- the offline form every shipped rpn.yaml / rcnn.yaml uses -- and the images are not read.  Both flags together give 3D boxes from
+a stereo pair in one call.  Training with DET3D_ON (PointRCNN's targets, losses and backward) is not built and raises.
 """
 from types import SimpleNamespace
 
@@ -39,17 +44,33 @@ class DispRCNN3D(nn.Module):
     def __init__(self, cfg):
         super().__init__()
         self.cfg = cfg
-        if getattr(cfg.MODEL, "DET3D_ON", False):
-            raise NotImplementedError("PointRCNN (MODEL.DET3D_ON) is downstream of the hot path and not built (SURVEY 2)")
-        d = cfg.MODEL.DISPNET
-        self.dispnet = PSMNet(d.MAX_DISP, d.MIN_DISP)
-        self.dispnet_lossfn = EndPointErrorLoss()
-        self.disp_resolution = d.RESOLUTIONS[0]
-        self.mask_threshold, self.mask_padding = 0.7, 1          # Masker(0.7, 1), reference :27
-        if getattr(d, "TRAINED_MODEL", ""):
-            self.dispnet.load_state_dict(torch.load(d.TRAINED_MODEL, "cpu")["model"])     # reference :29-32
-        self.register_buffer("_mean", torch.tensor(_MEAN, dtype=torch.float32), persistent=False)
-        self.register_buffer("_std", torch.tensor(_STD, dtype=torch.float32), persistent=False)
+        self.dispnet_on = bool(getattr(cfg.MODEL, "DISPNET_ON", True))
+        self.det3d_on = bool(getattr(cfg.MODEL, "DET3D_ON", False))
+        if self.dispnet_on:
+            d = cfg.MODEL.DISPNET
+            self.dispnet = PSMNet(d.MAX_DISP, d.MIN_DISP)
+            self.dispnet_lossfn = EndPointErrorLoss()
+            self.disp_resolution = d.RESOLUTIONS[0]
+            self.mask_threshold, self.mask_padding = 0.7, 1          # Masker(0.7, 1), reference :27
+            self._load_dispnet()                                     # reference :29-32
+            self.register_buffer("_mean", torch.tensor(_MEAN, dtype=torch.float32), persistent=False)
+            self.register_buffer("_std", torch.tensor(_STD, dtype=torch.float32), persistent=False)
+        if self.det3d_on:
+            from ..pointnet_module.point_rcnn.lib.net.point_rcnn import PointRCNN
+            self.pcnet = PointRCNN(cfg)
+            self._load_pcnet()                                       # reference :36-42
+
+    def _load_dispnet(self):
+        tm = getattr(self.cfg.MODEL.DISPNET, "TRAINED_MODEL", "") if self.dispnet_on else ""
+        if tm:
+            self.dispnet.load_state_dict(torch.load(tm, "cpu")["model"])
+
+    def _load_pcnet(self):
+        """MODEL.POINTRCNN.TRAINED_MODEL is a checkpoint of the wrapped stand-alone network: only its 'module.' keys count."""
+        tm = getattr(self.cfg.MODEL.POINTRCNN, "TRAINED_MODEL", "") if self.det3d_on else ""
+        if tm:
+            ckpt = torch.load(tm, "cpu")["model"]
+            self.pcnet.load_state_dict({k[len("module."):]: v for k, v in ckpt.items() if k.startswith("module.")})
 
     # ------------------------------------------------------------------ reference :286-294
     @staticmethod
@@ -95,16 +116,19 @@ class DispRCNN3D(nn.Module):
         return left, right, geom
 
     # ------------------------------------------------------------------ reference :266-284
-    def _forward_eval(self, left_images, right_images, left_result, right_result):
-        left, right, geom = self.prepare_psmnet_input(left_images, right_images, left_result, right_result)
-        if left.shape[0] > 0:
-            output = self.dispnet((left, right))
-        else:
-            output = torch.zeros(0, self.disp_resolution, self.disp_resolution, device=left.device)
-        counts = [len(a) for a in left_result]
-        for lr, o, gm in zip(left_result, torch.split(output, counts), torch.split(geom, counts)):
-            lr.add_field("disparity", o)             # ROI-normalised pixel units, as the reference
-            lr.add_field("roi_geom", gm)             # (x1, x1p, x2, x2p): offset x1-x1p and scale (x2-x1)/res for consumers
+    def _forward_eval(self, lr_images, left_result, right_result, left_targets=None):
+        if self.dispnet_on:
+            left, right, geom = self.prepare_psmnet_input(lr_images["left"], lr_images["right"], left_result, right_result)
+            if left.shape[0] > 0:
+                output = self.dispnet((left, right))
+            else:
+                output = torch.zeros(0, self.disp_resolution, self.disp_resolution, device=left.device)
+            counts = [len(a) for a in left_result]
+            for lr, o, gm in zip(left_result, torch.split(output, counts), torch.split(geom, counts)):
+                lr.add_field("disparity", o)             # ROI-normalised pixel units, as the reference
+                lr.add_field("roi_geom", gm)             # (x1, x1p, x2, x2p): offset x1-x1p and scale (x2-x1)/res for consumers
+        if self.det3d_on:                                # the images are not read here: without the PSMNet the results carry 'disparity'
+            left_result, right_result, _ = self.pcnet(left_result, right_result, left_targets)
         return {"left": left_result, "right": right_result}
 
     # ------------------------------------------------------------------ reference :192-207
@@ -193,18 +217,26 @@ class DispRCNN3D(nn.Module):
         return losses
 
     def forward(self, lr_images, lr_result, lr_targets=None):
+        if self.training and self.det3d_on:
+            raise NotImplementedError("DispRCNN3D with MODEL.DET3D_ON: PointRCNN training (SOLVER.TRAIN_PC: targets, losses, backward) is "
+                                      "not built; call .eval(), or train the disparity stage with DET3D_ON false")
+        if self.training and not self.dispnet_on:
+            raise NotImplementedError("DispRCNN3D without MODEL.DISPNET_ON has nothing to train")
         left_result, right_result = self.remove_illegal_detections(lr_result["left"], lr_result["right"])
         if self.training:
             if lr_targets is None:
                 raise ValueError("DispRCNN3D in training mode needs lr_targets (reference disprcnn3d.py:303)")
             return self._forward_train(lr_images["left"], lr_images["right"], left_result, right_result, lr_targets["left"])
-        return self._forward_eval(lr_images["left"], lr_images["right"], left_result, right_result)
+        if self.det3d_on and lr_targets is None:
+            raise ValueError("DispRCNN3D with MODEL.DET3D_ON needs lr_targets in evaluation too: lr_targets['left'] holds one BoxList with a "
+                             "'calib' field (or one calibration) per image")
+        return self._forward_eval(lr_images, left_result, right_result, lr_targets["left"] if lr_targets is not None else None)
 
     def load_state_dict(self, state_dict, strict=True):
-        """Reference :310-316: after loading a whole-detector checkpoint the disparity net is re-loaded from
-        MODEL.DISPNET.TRAINED_MODEL when that is set (the iDispNet weights trained stand-alone win)."""
+        """Reference :310-323: after loading a whole-detector checkpoint the disparity net is re-loaded from
+        MODEL.DISPNET.TRAINED_MODEL and the 3D stage from MODEL.POINTRCNN.TRAINED_MODEL when those are set (the weights trained
+        stand-alone win)."""
         ret = super().load_state_dict(state_dict, strict)
-        tm = getattr(self.cfg.MODEL.DISPNET, "TRAINED_MODEL", "")
-        if tm:
-            self.dispnet.load_state_dict(torch.load(tm, "cpu")["model"])
+        self._load_dispnet()
+        self._load_pcnet()
         return ret

@@ -7,15 +7,16 @@ instance.  Without an instance the fields are empty (`random` too, which the ref
 (`box3d` in 'xyzhwl_ry', `scores_3d`).  The reference writes that branch's fields to the first image only; here they are split over
 the images as the RCNN branch's are, which is the same for its one-image batches.
 
-The plumbing between the networks is plain torch on the device.  From the RPN's output to the end of `refine` nothing reads the
-device; the fields are then brought to the host in one copy (the reference's fields are CPU tensors too).
+The frame change between the networks is one kernel (`proposals_to_camera`; its torch composition is kept as
+`proposals_to_camera_unfused`, the comparator).  From the RPN's output to the end of `refine` nothing reads the device; the fields are
+then packed on the device and brought to the host in one copy (the reference's fields are CPU tensors too).
 
 The state-dict keys are the reference's (`rpn.*`, `rcnn_net.*`).  No training forward.
 """
 import torch
 import torch.nn as nn
 
-from disprcnn_amd.layers.rpn_proposals import points_depth
+from disprcnn_amd.layers.rpn_proposals import points_depth, rpn_to_camera
 from disprcnn_amd.modeling.pointcloud import InstancePointCloud
 from disprcnn_amd.structures.bounding_box_3d import Box3DList
 
@@ -43,11 +44,41 @@ def _attach(left_results, fields):
     return left_results
 
 
+def _to_host_once(*tensors):
+    """Device tensors -> CPU tensors of the same dtypes, shapes and values through ONE device-to-host copy: their bytes are packed on the
+    device, widest element first so that every part starts at a multiple of its element size."""
+    if not any(t.is_cuda for t in tensors):
+        return tuple(t.cpu() for t in tensors)
+    order = sorted(range(len(tensors)), key=lambda i: -tensors[i].element_size())
+    host = torch.cat([tensors[i].contiguous().view(-1).view(torch.uint8) for i in order]).cpu()
+    out, off = [None] * len(tensors), 0
+    for i in order:
+        n = tensors[i].numel() * tensors[i].element_size()
+        # a host copy of its own per tensor: torch.save refuses tensors of different dtypes that share one storage
+        out[i] = host[off:off + n].view(tensors[i].dtype).view(tensors[i].shape).clone()
+        off += n
+    return tuple(out)
+
+
 def combine_2d_3d(left_results, box, score, random):
     """box (R,7) 'ry_lhwxyz', score (R), random (R) of every instance in order -> fields on the left results (CPU tensors)."""
-    box, score, random = box.cpu(), score.cpu(), random.cpu()
+    box, score, random = _to_host_once(box, score, random)
     return _attach(left_results, {"box3d": (box, lambda v, lr: Box3DList(v, size=lr.size, mode="ry_lhwxyz")),
                                   "scores_3d": (score, None), "random": (random, None)})
+
+
+def proposals_to_camera_unfused(rpn_proposals, pts_mean, rot_angle):
+    """PointRCNN.proposals_to_camera as a composition of torch ops (a few dozen small launches): the comparator of the kernel in the tests
+    and in tools/bench_det3d.py.  Nothing in the product calls it."""
+    back = lambda p: InstancePointCloud.rotate_back(p + pts_mean[:, None, :], rot_angle)
+    out = dict(rpn_proposals)
+    out["backbone_xyz"] = back(rpn_proposals["backbone_xyz"])
+    out["pts_depth"] = points_depth(out["backbone_xyz"])
+    out["rpn_xyz"] = back(rpn_proposals["rpn_xyz"])
+    B = pts_mean.shape[0]
+    corners = Box3DList(rpn_proposals["roi_boxes3d"].reshape(-1, 7), (1, 1), "xyzhwl_ry").convert("corners").bbox_3d
+    out["roi_boxes3d"] = Box3DList(back(corners.view(B, -1, 3)).contiguous(), (1, 1), "corners").convert("xyzhwl_ry").bbox_3d.view(B, -1, 7)
+    return out
 
 
 class PointRCNN(nn.Module):
@@ -63,15 +94,15 @@ class PointRCNN(nn.Module):
         self.pointcloud = InstancePointCloud(npoints=self.cfg.RPN.NPOINTS, mask_threshold=0.5, mask_padding=1)    # _forward_val's Masker
 
     def proposals_to_camera(self, rpn_proposals, pts_mean, rot_angle):
-        """The RPN's dict in the centred, rotated frame of its clouds -> the same dict in the camera frame (point_rcnn.py:296-312)."""
-        back = lambda p: InstancePointCloud.rotate_back(p + pts_mean[:, None, :], rot_angle)
+        """The RPN's dict in the centred, rotated frame of its clouds -> the same dict in the camera frame (point_rcnn.py:296-312), one
+        kernel (layers/rpn_proposals.py:rpn_to_camera).  The input dict is left alone; what is not moved is passed through."""
         out = dict(rpn_proposals)
-        out["backbone_xyz"] = back(rpn_proposals["backbone_xyz"])
-        out["pts_depth"] = points_depth(out["backbone_xyz"])
-        out["rpn_xyz"] = back(rpn_proposals["rpn_xyz"])
-        B = pts_mean.shape[0]
-        corners = Box3DList(rpn_proposals["roi_boxes3d"].reshape(-1, 7), (1, 1), "xyzhwl_ry").convert("corners").bbox_3d
-        out["roi_boxes3d"] = Box3DList(back(corners.view(B, -1, 3)).contiguous(), (1, 1), "corners").convert("xyzhwl_ry").bbox_3d.view(B, -1, 7)
+        backbone, rpn, rois = rpn_proposals["backbone_xyz"], rpn_proposals["rpn_xyz"], rpn_proposals["roi_boxes3d"]
+        out["backbone_xyz"], out["pts_depth"], out["roi_boxes3d"] = rpn_to_camera(backbone, rois, pts_mean, rot_angle)
+        if rpn is backbone:                             # the RPN returns one tensor under both names
+            out["rpn_xyz"] = out["backbone_xyz"]
+        else:
+            out["rpn_xyz"] = rpn_to_camera(rpn, rois[:, :0], pts_mean, rot_angle)[0]
         return out
 
     def _forward_val(self, left_results, right_results, targets):

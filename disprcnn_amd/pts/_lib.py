@@ -39,6 +39,7 @@ _SIGS = {
     "drc_rpn_decode_proposals": (_I, [_L, _I, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
     "drc_rcnn_pool_canonical_fwd": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _F, _F, _P, _P, _P, _P, _P]),
     "drc_rcnn_decode_boxes": (_I, [_L, _I, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P]),
+    "drc_rpn_to_camera_fwd": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -62,47 +62,66 @@ def gather_predictions(predictions, fields=("scores", "labels", "disparity")):
     Reference: engine/inference.py:53-72 -- `all_gather` pickles every rank's dict (utils/comm.py:47-87: three collectives on a
     ByteTensor of the pickle).  Here the payload travels as tensors: one row-gather each for the per-image header
     (image id, width, height, ROI count), the boxes and every tensor field present on all images (first dim = ROIs).
-    Fields that are not tensors are not transported; duplicated image ids keep the copy of the highest rank, like
-    dict.update in the reference."""
+    A field that is a Box3DList on every image (`box3d`) travels as its `bbox_3d` rows plus its mode and is rebuilt per image with that
+    image's size; the mode must be one on all images of all ranks.  Other fields that are not tensors are not transported; duplicated
+    image ids keep the copy of the highest rank, like dict.update in the reference.  Every field is moved to the device of the boxes
+    before it travels and comes back there."""
     from ..structures.bounding_box import BoxList
+    from ..structures.bounding_box_3d import _MODES, Box3DList
+
+    def kind(i, f):                                # 1: tensor, 2: Box3DList, 0: absent or something else
+        if not predictions[i].has_field(f):
+            return 0
+        v = predictions[i].get_field(f)
+        return 1 if torch.is_tensor(v) else 2 if isinstance(v, Box3DList) else 0
+
     ids = sorted(predictions)
     dev = next((predictions[i].bbox.device for i in ids), torch.device("cpu"))
     head = torch.tensor([[i, predictions[i].size[0], predictions[i].size[1], len(predictions[i])] for i in ids],
                         dtype=torch.int64, device=dev).reshape(-1, 4)
     boxes = torch.cat([predictions[i].bbox for i in ids]) if ids else torch.zeros(0, 4, device=dev)
     # a field travels if every rank has it on every one of its images: agree on that with one small gather
-    have = torch.tensor([[int(all(predictions[i].has_field(f) and torch.is_tensor(predictions[i].get_field(f)) for i in ids))
-                          for f in fields]], dtype=torch.int64, device=dev)
+    kinds = [{kind(i, f) for i in ids} for f in fields]
+    have = torch.tensor([[int(k <= {1} or k == {2}) for k in kinds]], dtype=torch.int64, device=dev)
     have = all_gather_rows(have).min(dim=0)[0].tolist() if len(fields) else []
     head_all, boxes_all = all_gather_rows(head), all_gather_rows(boxes.float())
-    payload = {}
+    payload, box3d_mode = {}, {}
     for f, ok in zip(fields, have):
         if not ok:
             continue
         parts = [predictions[i].get_field(f) for i in ids]
+        # 0: plain tensors; 1 + k: Box3DLists of mode _MODES[k]; -1: Box3DLists of more than one mode on this rank (refused below, by all)
+        modes = sorted({_MODES.index(p_.mode) for p_ in parts if isinstance(p_, Box3DList)})
+        mode_code = 0 if not modes else 1 + modes[0] if len(modes) == 1 else -1
+        # every part on the boxes' device: the 3D stage attaches its fields as CPU tensors to results whose boxes are on the GPU, and a
+        # collective takes tensors of the group's device only
+        parts = [(p_.bbox_3d if isinstance(p_, Box3DList) else p_).to(dev) for p_ in parts]
         shape = next((tuple(p_.shape[1:]) for p_ in parts), None)
         dtype = next((p_.dtype for p_ in parts), None)
         # ranks without images learn the trailing shape AND the dtype from the others: gather both first (rank-independent
         # result) -- an empty payload of the wrong dtype would put mismatched byte sizes into all_gather
         meta = torch.tensor([[len(shape) if shape is not None else -1, _DTYPE_CODES.index(dtype) if dtype is not None else -1]
-                             + list(shape or ()) + [0] * (8 - len(shape or ()))], dtype=torch.int64, device=dev)
+                             + list(shape or ()) + [0] * (8 - len(shape or ())) + [mode_code]], dtype=torch.int64, device=dev)
         meta = all_gather_rows(meta)
         known = meta[meta[:, 0] >= 0]
         if len(known) == 0:
             continue
-        if bool((known[:, 1:] != known[0, 1:]).any()):
+        if bool((known[:, 1:] != known[0, 1:]).any()) or bool((known[:, -1] < 0).any()):
             raise RuntimeError(f"gather_predictions: field {f!r} has different dtypes / trailing shapes on different ranks")
         shape = tuple(int(v) for v in known[0, 2:2 + int(known[0, 0])])
         dtype = _DTYPE_CODES[int(known[0, 1])]
         local = torch.cat(parts) if parts else torch.zeros((0,) + shape, dtype=dtype, device=dev)
         payload[f] = all_gather_rows(local)
+        if int(known[0, -1]):
+            box3d_mode[f] = _MODES[int(known[0, -1]) - 1]
     if not is_main_process():
         return None
     out, start = {}, 0
     for img_id, w, h, r in head_all.tolist():
         bl = BoxList(boxes_all[start:start + r], (w, h))
         for f, t in payload.items():
-            bl.add_field(f, t[start:start + r])
+            v = t[start:start + r]
+            bl.add_field(f, Box3DList(v, (w, h), box3d_mode[f]) if f in box3d_mode else v)
         out[img_id] = bl
         start += r
     return [out[i] for i in sorted(out)]
@@ -124,10 +143,12 @@ def sharded_inference(model, samples, fields=("scores", "labels", "disparity"), 
     """The sharded inference loop of one node (reference: engine/inference.py:24-72 -- every rank runs the model on its share of the
     images, then the per-image predictions are gathered on the main process).
 
-    samples : a sequence of (image_id, lr_images, lr_result), the SAME on every rank (the reference reaches the same partition through
-              its DistributedSampler); this rank takes the contiguous `shard_range` of it.
-    model   : the detector (DispRCNN3D: forward(lr_images, lr_result) -> {"left": [BoxList], "right": [...]}); called once per sample of
-              the shard with NO collective in between -- ROIs and images are independent units.
+    samples : a sequence of (image_id, lr_images, lr_result) or (image_id, lr_images, lr_result, lr_targets), the SAME on every rank
+              (the reference reaches the same partition through its DistributedSampler); this rank takes the contiguous
+              `shard_range` of it.  A fourth item is handed to the model as its third argument: the 3D stage (MODEL.DET3D_ON)
+              reads the calibrations from it.
+    model   : the detector (DispRCNN3D: forward(lr_images, lr_result[, lr_targets]) -> {"left": [BoxList], "right": [...]}); called
+              once per sample of the shard with NO collective in between -- ROIs and images are independent units.
     Returns the left-view BoxLists of ALL samples ordered by image id on the main process, None on the others (gather_predictions: the
     [R,H,W] disparities travel as tensors, one row all_gather per field).  `timing` (a dict) receives compute_s / gather_s of this rank."""
     import time
@@ -135,8 +156,8 @@ def sharded_inference(model, samples, fields=("scores", "labels", "disparity"), 
     local = {}
     t0 = time.perf_counter()
     with torch.no_grad():
-        for image_id, lr_images, lr_result in samples[lo:hi]:
-            out = model(lr_images, lr_result)
+        for image_id, lr_images, lr_result, *lr_targets in samples[lo:hi]:
+            out = model(lr_images, lr_result, *lr_targets)
             left = out["left"] if isinstance(out, dict) else out
             local[int(image_id)] = left[0] if isinstance(left, (list, tuple)) else left
     if torch.cuda.is_available() and any(b.bbox.is_cuda for b in local.values()):

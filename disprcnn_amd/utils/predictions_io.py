@@ -4,9 +4,11 @@ Reference: disprcnn/engine/inference.py:125-133 -- `torch.save({'left': [BoxList
 (a plain list of BoxLists for the mono detectors), re-read with `torch.load(..., 'cpu')` by engine/inference.py:101-103 and
 data/datasets/kitti_car.py:51-57,102-106.  A BoxList is pickled by class path + instance dict: `bbox [R,4] f32`, `size (w, h)`, `mode`,
 `extra_fields {scores [R], labels [R], mask [R,1,28,28], disparity [R,224,224], ...}`, `PixelWise_map {name: DisparityMap}`,
-`mask_thresh` (disprcnn/structures/bounding_box.py:20-41).
+`mask_thresh` (disprcnn/structures/bounding_box.py:20-41).  The 3D stage adds a `box3d` field: a Box3DList with the instance dict
+`bbox_3d [R,7] f32`, `device`, `frame`, `mode`, `pose`, `ry`, `size` (disprcnn/structures/bounding_box_3d.py).
 
-The file written here names the REFERENCE's classes (`disprcnn.structures.bounding_box.BoxList`, `disprcnn.structures.disparity.DisparityMap`)
+The file written here names the REFERENCE's classes (`disprcnn.structures.bounding_box.BoxList`, `disprcnn.structures.disparity.DisparityMap`,
+`disprcnn.structures.bounding_box_3d.Box3DList`)
 so the reference's own `torch.load` reads it unchanged; the reader maps those class paths onto this package's classes and refuses every
 other global that is not part of torch's tensor serialisation -- a predictions file is data, not code."""
 import pickle
@@ -16,9 +18,11 @@ import types
 import torch
 
 from ..structures.bounding_box import BoxList
+from ..structures.bounding_box_3d import Box3DList
 from ..structures.disparity import DisparityMap
 
-_REF = {BoxList: ("disprcnn.structures.bounding_box", "BoxList"), DisparityMap: ("disprcnn.structures.disparity", "DisparityMap")}
+_REF = {BoxList: ("disprcnn.structures.bounding_box", "BoxList"), DisparityMap: ("disprcnn.structures.disparity", "DisparityMap"),
+        Box3DList: ("disprcnn.structures.bounding_box_3d", "Box3DList")}
 _OURS = {v: k for k, v in _REF.items()}
 # what a tensor-bearing pickle legitimately references (torch.save's own rebuild helpers and containers)
 _ALLOWED = {("collections", "OrderedDict"), ("torch._utils", "_rebuild_tensor_v2"), ("torch._utils", "_rebuild_parameter"),
@@ -62,7 +66,7 @@ class _PickleModule:
 
 def _export(obj, stubs):
     """The tree with detached CPU copies of every tensor (the reference gathers predictions to the CPU before saving, inference.py:44-50)
-    and every BoxList / DisparityMap replaced by an instance of the stand-in class carrying the reference's class path and the same
+    and every BoxList / DisparityMap / Box3DList replaced by an instance of the stand-in class carrying the reference's class path and the same
     instance dict: pickling it emits byte for byte what pickling the reference's object emits (NEWOBJ + BUILD)."""
     if torch.is_tensor(obj):
         return obj.detach().cpu()
@@ -73,6 +77,10 @@ def _export(obj, stubs):
         if isinstance(obj, BoxList):
             state.setdefault("mask_thresh", 0.5)                       # the reference's constructor sets it (bounding_box.py:40)
             state["size"] = tuple(int(v) for v in obj.size)
+        if isinstance(obj, Box3DList):                                 # the reference's seven keys; its tensor is on the CPU now
+            state["device"] = torch.device("cpu")
+            state.setdefault("pose", None)
+            state.setdefault("ry", None)
         out.__dict__.update(state)
         return out
     if isinstance(obj, dict):
@@ -109,12 +117,16 @@ def save_predictions(predictions, path):
 
 
 def load_predictions(path, map_location="cpu"):
-    """Read a predictions file written by the reference or by save_predictions into this package's BoxList / DisparityMap."""
+    """Read a predictions file written by the reference or by save_predictions into this package's BoxList / DisparityMap / Box3DList."""
     out = torch.load(path, map_location=map_location, pickle_module=_PickleModule, weights_only=False)
     for bl in _boxlists(out):
         bl.size = tuple(bl.size)
         bl.__dict__.setdefault("extra_fields", {})
         bl.__dict__.setdefault("PixelWise_map", {})
+        for v in bl.extra_fields.values():
+            if isinstance(v, Box3DList):
+                v.size = tuple(v.size)
+                v.device = v.bbox_3d.device
     return out
 
 

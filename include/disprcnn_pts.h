@@ -153,6 +153,19 @@ int drc_rcnn_decode_boxes(int64_t n, int R, const float* rois, const float* reg,
                           float half_y_bin, float loc_y_scope, float angle_per_class, float half_angle, float quarter_pi, float anchor_h,
                           float anchor_w, float anchor_l, float* boxes, float* bev, float* norm_score, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The frame change between the two networks (pts/frame_ops.hip; point_rcnn.py:296-312): the RPN's outputs, in the centred and rotated
+ * frame of each instance cloud, back to the rectified camera frame.  One launch:
+ *   xyz [B,N,3], boxes [B,M,7] as [x,y,z,h,w,l,ry], mean [B,3] fp32, rot [B] fp64 (the angle InstancePointCloud rotated the cloud by)
+ *   xyz_cam [B,N,3] <- (p + mean) rotated about y by -rot; cos and sin of -rot are taken in fp64 and rounded once to fp32
+ *   depth   [B,N]   <- |xyz_cam| with the rounding of drc_rpn_points_depth
+ *   boxes_cam [B,M,7] <- the box through its corners as Box3DList does it, in fp32 and in that order: corners of the centred box, + mean,
+ *                      the rotation, then centre = (c7 + c0) / 2, l, h, w = |c0 - c3|, |c0 - c1|, |c0 - c4|, ry = -atan2 of the edge 0 -> 3.
+ *                      An all-zero padding box comes back as the rotated mean with zero size and ry = -0.0.
+ * Nothing is launched when B = 0 or N = M = 0; with only one of N, M zero the other part is still written. */
+int drc_rpn_to_camera_fwd(int B, int N, int M, const float* xyz, const float* boxes, const float* mean, const double* rot, float* xyz_cam,
+                          float* depth, float* boxes_cam, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
