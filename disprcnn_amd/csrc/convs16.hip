@@ -29,14 +29,16 @@
 //   the three output planes the slab touches.  A finished plane's accumulator is exchanged between the K-split waves through LDS
 //   (each keeps 16/KW registers = the couts it stores), one barrier per step; BN / residual / ReLU / hi-lo split run in the shadow of
 //   the next plane's MFMAs.
-// CV = the first layer: the slab rows are built from the left / right feature maps (RS16 2D) -- left where the shifted pixel exists,
-// right moved by lo4 + plane columns, everything else fetched from the zero halo -- so the 64-channel volume never exists.
+// CV = the first layer (the concat cost volume of the left / right RS16 2D feature maps is its virtual input: the 64-channel volume never
+// exists).  It does not walk the depth: s16_cvrows.h computes it from per-row 2D tap maps (round 8), one row per work item here,
+// two in convs16w.hip, bit-identical.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <type_traits>
 
 #include "../../include/disprcnn_hip.h"
+#include "s16_cvrows.h"
 #include "s16_ovf.h"
 #include "s16_tilemap.h"
 
@@ -74,12 +76,18 @@ constexpr int RING = 3;
 template <int KW, bool CV, int RT = 1, int WT = 28, bool RES = false, bool Y32 = false, bool HEAD = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void convs16_kernel(const drc_s16conv_params p) {
     static_assert(!HEAD || (KW == 2 && !CV && RT == 1 && !RES && !Y32), "the fused cout-1 head is a form of the 32 -> 32 full-resolution layer");
+    static_assert(!CV || (KW == 4 && RT == 1 && WT == 28 && !RES && !Y32), "the cost-volume form: 64 virtual input channels, full-resolution rows, RS16 output");
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    if constexpr (CV) {
+        s16cv::s16_cvrows_run<1>(p, lds);      // (everything below is the depth walk of the layers whose input is a real tensor)
+        return;
+    }
     constexpr int TX = WT;                      // output columns per tile
     constexpr int SX = WT + 2;                  // staged columns (TX + halo)
     constexpr int RPW = 4 / KW;                 // MFMA tiles per workgroup (RPW * RT output rows)
     constexpr int CBI = KW / 2;                 // 32-channel input blocks
     constexpr int SROWS = RPW * RT + 2;
-    static_assert(RT * WT <= 32 && (RT == 1 || !CV), "tile shape");
+    static_assert(RT * WT <= 32, "tile shape");
     constexpr int SLAB = CBI * 8 * CPB;
     constexpr int NL = CBI * 8 * (PV / 64) / 4; // LDS-DMA instructions per wave and slab
     constexpr int OWN = 16 / KW;                // accumulator registers (couts per lane) a wave finishes
@@ -88,7 +96,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     constexpr int NS = 2;                       // stores per step (RS16 hi, lo | blocked fp32 x2)
     static_assert(!(Y32 && (KW != 2 || RES)), "the blocked fp32 output exists for the 32-channel layers without residual");
     static_assert(RT == 1 ? SROWS * SX + 4 <= PV : (SROWS + 1) * SX + 4 <= PV, "slab plane too small (incl. the rows / columns the idle lanes over-read)");
-    extern __shared__ __attribute__((aligned(16))) char lds[];
     char* ring = lds;
     char* xchg = lds + RING * SLAB;             // [2 parities][4 waves][XW]
     char* pbuf = xchg + 2 * 4 * XW;             // HEAD: [2 parities][2 tiles][XW] the K-slice-1 halves of P
@@ -98,7 +105,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int n_ = lane & 31, g = lane >> 5;
     // this lane's voxel inside the MFMA tile: row-major (lanes >= RT * WT idle).  lo4 bit 8 of a non-CV launch selects the bank-conflict-free
     // order of s16_tilemap.h -- measured slower (its stores are less coalesced, the LDS reads were not the limit): an experiment, not the product
-    const S16TileLane tln = s16_tile_lane<RT, WT>(n_, CV || !(p.lo4 & 0x100));
+    const S16TileLane tln = s16_tile_lane<RT, WT>(n_, !(p.lo4 & 0x100));
     const int rl = tln.rl, xl = tln.xl;
     const int r = wave / KW, k = wave % KW;     // MFMA tile of the workgroup, K slice
     const int n_ct = p.cout / 32;
@@ -113,7 +120,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const long xnB = (long)CBI * xcbB;
     const int cbo = p.cout / 32;
     const long ynB = (long)cbo * xcbB;          // RS16 output / residual: same spatial geometry
-    const long mapnB = planeB;                  // 2D feature maps (one 32-channel block, no depth halo)
     // blocked fp32 output: float[N][cout/16][D+2][H+2][W+2][16]
     const long b_rowB = (long)Wp * 64, b_planeB = (long)Hp * b_rowB, b_cbB = (long)(D + 2) * b_planeB, b_nB = (long)(p.cout / 16) * b_cbB;
 
@@ -183,53 +189,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         c.x0 = xt * TX;
         return c;
     };
-    // staging source of a column: the unit's input (CV: its left / right maps) as buffer bases + this lane's byte offsets of its two
-    // staged voxels (h = 0, 1); the plane / channel-block / chunk offset of an instruction is a scalar (soffset)
-    struct Src { const char* a; const char* b; unsigned v0, v1; int x0; };
+    // staging source of a column: the unit's input as a buffer base + this lane's byte offsets of its two staged voxels (h = 0, 1); the
+    // plane / channel-block / chunk offset of an instruction is a scalar (soffset)
+    struct Src { const char* a; unsigned v0, v1; };
     auto src_of = [&](const Col& c) __attribute__((always_inline)) {
         Src q;
-        if constexpr (CV) {
-            q.a = (const char*)p.left + (long)c.n * mapnB;
-            q.b = (const char*)p.right + (long)c.n * mapnB;
-            q.v0 = (unsigned)((long)(c.y0 + srcrow[0]) * rowB);
-            q.v1 = (unsigned)((long)(c.y0 + srcrow[1]) * rowB);
-        } else {
-            q.a = (const char*)p.x + (long)c.n * xnB;
-            q.b = nullptr;
-            q.v0 = (unsigned)((long)(c.y0 + srcrow[0]) * rowB + (long)(c.x0 + srcx[0]) * 16);
-            q.v1 = (unsigned)((long)(c.y0 + srcrow[1]) * rowB + (long)(c.x0 + srcx[1]) * 16);
-        }
-        q.x0 = c.x0;
+        q.a = (const char*)p.x + (long)c.n * xnB;
+        q.v0 = (unsigned)((long)(c.y0 + srcrow[0]) * rowB + (long)(c.x0 + srcx[0]) * 16);
+        q.v1 = (unsigned)((long)(c.y0 + srcrow[1]) * rowB + (long)(c.x0 + srcx[1]) * 16);
         return q;
     };
     auto stage = [&](const Src& q, int pl, int slot) __attribute__((always_inline)) {       // input plane pl of a column -> ring slot
         char* dst = ring + slot * SLAB;
         const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)q.a, 0, 0x7FFFFF00, 0x00020000);
-        unsigned va[2] = {q.v0, q.v1}, vb[2] = {q.v0, q.v1};
-        if constexpr (CV) {
-            const int ish = p.lo4 + pl;
-            const bool real = pl < D;                                                  // a phantom plane of the cost volume is zero as well
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int xlog = q.x0 + srcx[h] - 1;                                   // logical column
-                const bool ok = real && srcok[h] && xlog >= 0 && xlog < W && xlog - ish >= 0 && xlog - ish < W;
-                va[h] += ok ? (unsigned)((q.x0 + srcx[h]) * 16) : 0u;                  // column 0 = the zero halo
-                vb[h] += ok ? (unsigned)((q.x0 + srcx[h] - ish) * 16) : 0u;
-            }
-        }
-        const __amdgpu_buffer_rsrc_t rb = CV ? __builtin_amdgcn_make_buffer_rsrc((void*)q.b, 0, 0x7FFFFF00, 0x00020000) : ra;
+        const unsigned va[2] = {q.v0, q.v1};
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
             const int id = wave * NL + i;
             const int cb = id >> 4, c = (id >> 1) & 7, h = id & 1;
-            if constexpr (CV) {
-                const int so = c * (Wp * 16);
-                if (cb) __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, LDS_PTR(dst + (cb * 8 + c) * CPB + h * 1024), 16, vb[h], so, 0, 0);
-                else __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, LDS_PTR(dst + (cb * 8 + c) * CPB + h * 1024), 16, va[h], so, 0, 0);
-            } else {
-                const int so = (int)((long)cb * xcbB + (long)(pl + 1) * planeB + (long)c * (Wp * 16));
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, LDS_PTR(dst + (cb * 8 + c) * CPB + h * 1024), 16, va[h], so, 0, 0);
-            }
+            const int so = (int)((long)cb * xcbB + (long)(pl + 1) * planeB + (long)c * (Wp * 16));
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, LDS_PTR(dst + (cb * 8 + c) * CPB + h * 1024), 16, va[h], so, 0, 0);
         }
     };
     // output context of a column: unit bases + this lane's voxel offsets (plane 0, padded coordinates + 1)
@@ -326,8 +305,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const bool nxt = tp >= Dw;
             Src q;
             q.a = nxt ? s_next.a : s_cur.a;
-            q.b = nxt ? s_next.b : s_cur.b;
-            q.x0 = nxt ? s_next.x0 : s_cur.x0;
             q.v0 = nxt ? s_next.v0 : s_cur.v0;
             q.v1 = nxt ? s_next.v1 : s_cur.v1;
             int pl = nxt ? tp - Dw : tp;
@@ -579,7 +556,7 @@ int launch2(const drc_s16conv_params& p, hipStream_t stream) {
     constexpr int CBI = KW / 2;
     constexpr int SLAB = CBI * 8 * CPB;
     constexpr int XW = 4096;
-    constexpr size_t lds = RING * SLAB + 2 * 4 * XW + (HEAD ? 2 * 2 * XW : 0);
+    constexpr size_t lds = CV ? (size_t)s16cv::LDS_BYTES : RING * SLAB + 2 * 4 * XW + (HEAD ? 2 * 2 * XW : 0);
     static_assert(lds <= 160 * 1024, "LDS");
     static bool attr_done = false;
     if (!attr_done) {
@@ -592,6 +569,7 @@ int launch2(const drc_s16conv_params& p, hipStream_t stream) {
     const int n_ct = p.cout / 32;
     long blocks = 256;                                   // column workers x cout tiles (the tiles of a worker side by side on its XCD)
     while (blocks > 8 * n_ct && blocks / (2 * n_ct) >= columns) blocks /= 2;
+    if constexpr (CV) blocks = s16cv::s16_cvrows_blocks<1>(p);      // (its work items are rows, not columns of rows)
     hipLaunchKernelGGL((convs16_kernel<KW, CV, RT, WT, RES, Y32, HEAD>), dim3((unsigned)blocks), dim3(256), lds, stream, p);
     return (int)hipGetLastError();
 }

@@ -1370,7 +1370,7 @@ def cost_volume16_blocked(left, right, out, lo4, hi4, in_blocked_pad=-1):
 HEAD_FUSED = {"enabled": True}       # eval, split-f16 regressor: classif[0] + the 32 -> 1 layer as one fused launch + a gather (convs16.hip HEAD form) instead of a blocked fp32 tensor + cout1_mfma.hip
 LASTCONV_S16 = {"enabled": True}     # eval, split-f16 2D schedule: lastconv[0] (320 -> 128) as three chained split-f16 launches over the concat's parts (runtime._ws2d_s16)
 S16 = {"enabled": True}       # eval: the stride-1 3x3x3 layers at full resolution on the f16 matrix cores in split arithmetic (convs16.hip)
-CV_WIDE = {"enabled": True}   # eval, large batches: the cost-volume layer on the two-tiles-per-wave kernel (convs16w.hip); False: convs16.hip's one-tile form (A/B switch)
+CV_WIDE = {"enabled": True}   # eval, large batches: the cost-volume layer with two rows per work item (convs16w.hip); False: convs16.hip's one-row form (A/B switch, read at every run())
 
 
 
@@ -1600,13 +1600,12 @@ class ConvPlanS16:
         if kind == "s1":
             self._kfmt = "convs16_kernel<%d,%s,%d,%d,%%s,%%s,%%s>" % (cin // 16, "true" if cv else "false", rt, wt)
             self.kname = self._kfmt % ("false", "false", "false")  # (the residual / blocked-fp32-output / fused-head template flags follow the call's arguments)
-            # round 6: the cost-volume form runs two tiles per wave (convs16w.hip) where the launch has enough whole two-row blocks: the
-            # library decides (drc_conv3d_k3_s16_wide), asked here with stand-in pointers
+            # the cost-volume form takes two rows per work item (convs16w.hip) where the launch has enough whole two-row blocks: the library
+            # decides (drc_conv3d_k3_s16_wide), asked here with stand-in pointers; CV_WIDE is read at every run(), so a toggle after the plan
+            # exists takes effect (`kname` names the kernel of the switch's state at construction)
             from ._lib import DrcS16ConvParams
             probe = DrcS16ConvParams(None if cv else 1, 1, 1, 1, None, 1, None, 1 if cv else None, 1 if cv else None, N, D, H, W, cin, cout, int(bool(relu)), 0, 1)
-            self._wide = bool(CV_WIDE["enabled"] and _lib.lib().drc_conv3d_k3_s16_wide(C.byref(probe)))
-            if cv and not CV_WIDE["enabled"]:
-                self.dil = 0x800               # (the library's experiment bit of the 3D layers' unused `dil` field: keep the one-tile kernel)
+            self._wide_ok = bool(_lib.lib().drc_conv3d_k3_s16_wide(C.byref(probe)))
             self._wname = "convs16w_kernel<%d,%s>" % (cin // 16, "true" if cv else "false")
             if self._wide:
                 self.kname = self._wname
@@ -1624,6 +1623,10 @@ class ConvPlanS16:
             self.kname = "convs16d_kernel<%d,%d,%d,%d,true,%s>" % (cin // 16, rt, wt, ring, "true" if cs else "false")
         else:
             self.kname = "convs16u_kernel<%d,%d>" % (rt, wt)
+
+    @property
+    def _wide(self):
+        return self.kind == "s1" and self._wide_ok and bool(CV_WIDE["enabled"])
 
     def run(self, x16, w16, scale, shift, y16=None, y32=None, res=None, left=None, right=None, lo4=0, head=None):
         """head = (packed 32 -> 1 weights of s16.pack_head_weight_s16, S buffer fp32 of >= N*D*H*W*12 floats): the layer is classif[0] of a
@@ -1654,7 +1657,8 @@ class ConvPlanS16:
         p = DrcS16ConvParams(_ptr(x16.storage) if x16 is not None else None, _ptr(w16), _ptr(scale), _ptr(shift),
                              _ptr(res.storage) if res is not None else None, _ptr(y16.storage) if y16 is not None else None,
                              _ptr(y32.storage) if y32 is not None else None, _ptr(left.storage) if self.cv else None,
-                             _ptr(right.storage) if self.cv else None, self.N, self.D, self.H, self.W, self.cin, self.cout, int(self.relu), int(lo4), int(self.dil),
+                             _ptr(right.storage) if self.cv else None, self.N, self.D, self.H, self.W, self.cin, self.cout, int(self.relu), int(lo4),
+                             0x800 if (self.cv and self.kind == "s1" and not CV_WIDE["enabled"]) else int(self.dil),   # (the library's experiment bit of the 3D layers' unused `dil` field: keep the one-row kernel)
                              _ptr(head[1]) if head is not None else None, _ptr(head[0]) if head is not None else None, _ovf_ptr())
         dev = self.device
         if TIMING is not None:

@@ -808,7 +808,7 @@ class PSMNetRuntime:
         m = self.model
         return (m.maxdisp, m.mindisp, getattr(m, "regressor_math", "auto"), getattr(m, "regressor_storage", "f32"),
                 getattr(m, "feature_storage", "f32"), getattr(m, "feature_math", "auto"),
-                E.S16["enabled"], E.HEAD_FUSED["enabled"], E.LASTCONV_S16["enabled"], E.TRUNK_S16["enabled"], E.s16_allowed(),
+                E.S16["enabled"], E.HEAD_FUSED["enabled"], E.LASTCONV_S16["enabled"], E.TRUNK_S16["enabled"], E.CV_WIDE["enabled"], E.s16_allowed(),
                 id(E.guard_in_scope()))
 
     def forward_features(self, fl, fr, out_hw, training=False):

@@ -11,8 +11,6 @@ from disprcnn_amd.utils import synth
 dev = torch.device("cuda:0")
 if os.environ.get("W2D_MIN_CHUNKS"):
     E.WINO2D["min_chunks"] = int(os.environ["W2D_MIN_CHUNKS"])
-if os.environ.get("T2D_TILE"):
-    E.TAP2D["tile"] = tuple(int(v) for v in os.environ["T2D_TILE"].split(","))
 bb = build_backbone(NS(MODEL=NS(BACKBONE=NS(CONV_BODY="R-50-FPN"), RESNETS=NS(BACKBONE_OUT_CHANNELS=256, RES2_OUT_CHANNELS=256))))
 bb.load_state_dict(synth.synth_backbone_state(bb.state_dict()))
 bb = bb.to(dev).eval()
