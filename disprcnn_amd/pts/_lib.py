@@ -15,6 +15,7 @@ _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
 _F = C.c_float
+_D = C.c_double
 _SIGS = {
     "drc_pts_version": (C.c_char_p, []),
     "drc_instance_points_fwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _F, _I, _P, _P, _L, _P]),
@@ -40,6 +41,13 @@ _SIGS = {
     "drc_rcnn_pool_canonical_fwd": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _F, _F, _P, _P, _P, _P, _P]),
     "drc_rcnn_decode_boxes": (_I, [_L, _I, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P]),
     "drc_rpn_to_camera_fwd": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "drc_kitti_eval_max_det": (_I, []),
+    "drc_kitti_eval_max_gt": (_I, []),
+    "drc_kitti_eval_clean": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "drc_kitti_eval_overlaps": (_I, [_I, _L, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "drc_kitti_eval_pass1": (_I, [_I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _D, _D, _D, _P, _P, _P]),
+    "drc_kitti_eval_pass2": (_I, [_I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _D, _D, _D, _I, _P, _P, _P, _P, _P]),
+    "drc_kitti_eval_reduce": (_I, [_I, _P, _P, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

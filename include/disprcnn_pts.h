@@ -166,6 +166,48 @@ int drc_rcnn_decode_boxes(int64_t n, int R, const float* rois, const float* reg,
 int drc_rpn_to_camera_fwd(int B, int N, int M, const float* xyz, const float* boxes, const float* mean, const double* rot, float* xyz_cam,
                           float* depth, float* boxes_cam, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * KITTI object scoring (pts/kitti_eval.hip; the KITTI devkit's evaluate_object.cpp): 2D, AOS, BEV and 3D precision at 41 recall samples.
+ * ALL arithmetic and all floating-point buffers here are fp64, as the devkit's.
+ *
+ * Ragged input in CSR form over F frames: frame f owns ground-truth rows gt_off[f] .. gt_off[f+1] (DontCare rows included), detections
+ * det_off[f] .. det_off[f+1] and the G_f * D_f pairs pair_off[f] + g * D_f + d (gt_off, det_off [F+1] int32, pair_off [F+1] int64).
+ *   gt  [NG,14]: truncation, occlusion, alpha, x1, y1, x2, y2, h, w, l, t1, t2, t3, ry      gt_cls  [NG] int32: 0 the class under
+ *   det [ND,13]: alpha, x1, y1, x2, y2, h, w, l, t1, t2, t3, ry, score                       evaluation, 1 its neighbour class (Van for
+ *   Car, Person_sitting for Pedestrian), 2 DontCare, 3 any other; det_cls [ND] int32: 0 the class under evaluation, 1 any other.
+ * Per-frame limits: at most drc_kitti_eval_max_det() = 256 detections (the assigned-detection set is a bit mask of 4 x 64 bits) and
+ * drc_kitti_eval_max_gt() = 4096 ground-truth rows.  The caller passes the largest per-frame counts (max_gt, max_det), which it knows
+ * from the offsets it built; beyond the limits the status is -3 and nothing is launched.
+ * Indices below: d = difficulty (easy, moderate, hard), m = metric (0 image, 1 ground, 2 3d), t = recall sample 0..40; metric_mask bit m
+ * set = metric m is evaluated (the others are neither computed nor written, except where stated).
+ * ------------------------------------------------------------------------------------- */
+int drc_kitti_eval_max_det(void);
+int drc_kitti_eval_max_gt(void);
+/* cleanData: gt_ign [3,NG], det_ign [3,ND] int8 <- 0 valid, 1 ignored (may absorb a match without counting), -1 skipped */
+int drc_kitti_eval_clean(int NG, int ND, const double* gt, const int32_t* gt_cls, const double* det, const int32_t* det_cls,
+                         int8_t* gt_ign, int8_t* det_ign, void* stream);
+/* ov [3,NP] <- per pair the image IoU, the rotated BEV IoU (centre t1, t3; extents l, w; angle ry) and the 3D IoU (BEV intersection times
+ * the overlap of [t2 - h, t2]); for a DontCare row the intersection over the detection's own area / volume (the devkit's criterion 0). */
+int drc_kitti_eval_overlaps(int F, int64_t NP, const double* gt, const int32_t* gt_cls, const double* det, const int32_t* gt_off,
+                            const int32_t* det_off, const int64_t* pair_off, int metric_mask, double* ov, void* stream);
+/* computeStatistics without false positives, one thread per (frame, d, m): matched [3,3,NG] int8 <- 1 where the ground-truth row counts
+ * as a true positive (every element is written), v [3,3,NG] <- the score of its detection (written where matched is 1 only). */
+int drc_kitti_eval_pass1(int F, int NG, int ND, int64_t NP, int max_gt, int max_det, const double* gt, const int32_t* gt_cls,
+                         const double* det, const int32_t* gt_off, const int32_t* det_off, const int64_t* pair_off,
+                         const int8_t* gt_ign, const int8_t* det_ign, const double* ov, int metric_mask, double min_overlap_image,
+                         double min_overlap_ground, double min_overlap_3d, double* v, int8_t* matched, void* stream);
+/* computeStatistics with false positives, one thread per (frame, d, m, t): thresholds [3,3,41], of which the first n_thresholds [3,3]
+ * (int32) are used.  counts [3,3,41,3,F] int16 <- tp, fp, fn of each frame (the per-frame limits keep them below 2^15); sim [3,3,41,F] <- its orientation-similarity sum (metric 0
+ * with compute_aos != 0; 0 for a frame without tp and fp).  Every element is written (0 for a metric or a sample that is not used). */
+int drc_kitti_eval_pass2(int F, int NG, int ND, int64_t NP, int max_gt, int max_det, const double* gt, const int32_t* gt_cls,
+                         const double* det, const int32_t* gt_off, const int32_t* det_off, const int64_t* pair_off,
+                         const int8_t* gt_ign, const int8_t* det_ign, const double* ov, int metric_mask, double min_overlap_image,
+                         double min_overlap_ground, double min_overlap_3d, int compute_aos, const double* thresholds,
+                         const int32_t* n_thresholds, int16_t* counts, double* sim, void* stream);
+/* out_counts [3,3,41,3] int64, out_sim [3,3,41] <- the sums over the frames, in an order that depends on F alone (no atomics):
+ * bit-identical run to run. */
+int drc_kitti_eval_reduce(int F, const int16_t* counts, const double* sim, int64_t* out_counts, double* out_sim, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
