@@ -16,6 +16,7 @@ The state-dict keys are the reference's (`rpn.*`, `rcnn_net.*`).  No training fo
 import torch
 import torch.nn as nn
 
+from disprcnn_amd.layers.pointrcnn_loss import rpn_point_labels
 from disprcnn_amd.layers.rpn_proposals import points_depth, rpn_to_camera
 from disprcnn_amd.modeling.pointcloud import InstancePointCloud
 from disprcnn_amd.structures.bounding_box_3d import Box3DList
@@ -79,6 +80,19 @@ def proposals_to_camera_unfused(rpn_proposals, pts_mean, rot_angle):
     corners = Box3DList(rpn_proposals["roi_boxes3d"].reshape(-1, 7), (1, 1), "xyzhwl_ry").convert("corners").bbox_3d
     out["roi_boxes3d"] = Box3DList(back(corners.view(B, -1, 3)).contiguous(), (1, 1), "corners").convert("xyzhwl_ry").bbox_3d.view(B, -1, 7)
     return out
+
+
+def generate_rpn_training_labels(pts, targets):
+    """The RPN's per-point training labels: pts (B,N,3) and, per cloud, a BoxList whose `box3d` field holds its one ground-truth box
+    -> cls_label (B,N): 1 inside the box, -1 inside only the box enlarged by 0.2 (ignored), else 0; reg_label (B,N,7): centre - p (the
+    centre at half height), h, w, l, ry on the inside points, zero elsewhere.  The boxes go through Box3DList as the reference's do; the
+    inside tests and the labels of all clouds are one kernel (layers/pointrcnn_loss.py:rpn_point_labels)."""
+    box3d = [target.get_field('box3d') for target in targets]
+    gt_boxes3d = torch.cat([b.convert('xyzhwl_ry').bbox_3d for b in box3d])
+    gt_corners = torch.cat([b.convert('corners').bbox_3d.view(-1, 8, 3) for b in box3d])
+    extend_box_corners = torch.cat([b.enlarge_box3d(0.2).convert('corners').bbox_3d.view(-1, 8, 3) for b in box3d])
+    dev = pts.device
+    return rpn_point_labels(pts, gt_boxes3d.to(dev), gt_corners.to(dev), extend_box_corners.to(dev))
 
 
 class PointRCNN(nn.Module):

@@ -41,6 +41,14 @@ _SIGS = {
     "drc_rcnn_pool_canonical_fwd": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _F, _F, _P, _P, _P, _P, _P]),
     "drc_rcnn_decode_boxes": (_I, [_L, _I, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P]),
     "drc_rpn_to_camera_fwd": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "drc_train_scratch_doubles": (_I, []),
+    "drc_rpn_point_labels": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "drc_bin_reg_targets": (_I, [_L, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "drc_bin_reg_loss_fwd": (_I, [_L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "drc_bin_reg_loss_bwd": (_I, [_L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "drc_point_cls_loss_fwd": (_I, [_L, _I, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P]),
+    "drc_point_cls_loss_bwd": (_I, [_L, _I, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P]),
+    "drc_focal_elementwise": (_I, [_L, _P, _P, _P, _F, _F, _P, _P, _P]),
     "drc_kitti_eval_max_det": (_I, []),
     "drc_kitti_eval_max_gt": (_I, []),
     "drc_kitti_eval_clean": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P]),

@@ -83,6 +83,14 @@ class Box3DList(object):
         bbox_3d = torch.cat((xyz, h, w, l, ry), dim=-1) if mode == "xyzhwl_ry" else torch.cat((ry, l, h, w, xyz), dim=-1)
         return Box3DList(bbox_3d, self.size, mode=mode)
 
+    def enlarge_box3d(self, extra_width):
+        """The boxes grown by extra_width on every side (h, w, l + 2 extra_width, the bottom centre moved down by extra_width), in this
+        list's mode; through 'xyzhwl_ry' and back, as the reference's."""
+        large_boxes3d = self.convert("xyzhwl_ry").bbox_3d.clone()
+        large_boxes3d[:, 3:6] += extra_width * 2
+        large_boxes3d[:, 1] += extra_width
+        return Box3DList(large_boxes3d, self.size, mode="xyzhwl_ry").convert(self.mode)
+
     def __repr__(self):
         return "{}(num_boxes_3d={}, image_width={}, image_height={}, mode={})".format(self.__class__.__name__, len(self), self.size[0],
                                                                                       self.size[1], self.mode)

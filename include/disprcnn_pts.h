@@ -154,6 +154,59 @@ int drc_rcnn_decode_boxes(int64_t n, int R, const float* rois, const float* reg,
                           float anchor_w, float anchor_l, float* boxes, float* bev, float* norm_score, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * PointRCNN training labels and losses (pts/train_targets.hip; net/point_rcnn.py:generate_rpn_training_labels, utils/loss_utils.py,
+ * net/rpn_loss.py, net/rcnn_loss.py).  Labels are the reference's fp32 expressions in its order; loss values are evaluated and summed in
+ * fp64 (per-block partials added in block order, no atomics: bit-identical run to run) and rounded once.  No entry synchronises.
+ * `scratch`: drc_train_scratch_doubles() doubles of workspace, contents need not be set.
+ * ------------------------------------------------------------------------------------- */
+int drc_train_scratch_doubles(void);
+/* pts [B,N,3], one ground-truth box per cloud: boxes [B,7] as [x,y,z,h,w,l,ry], its corners [B,8,3] and the corners of the box enlarged
+ * by 0.2 [B,8,3] -> cls_label [B,N] (1 inside, -1 where the two inside tests differ, else 0), reg_label [B,N,7] (centre - p with
+ * centre.y = y - h / 2, then h, w, l, ry; zero on points that are not inside).  Inside (filter_bbox_3d): 0 < m < v.v, strictly, for the
+ * dot products m of p - c4 with the edges v = c5 - c4, c0 - c4, c7 - c4.  Every element is written.  B <= 65535. */
+int drc_rpn_point_labels(int B, int N, const float* pts, const float* boxes, const float* corners, const float* corners_large,
+                         float* cls_label, float* reg_label, void* stream);
+/* get_reg_loss.  pred_reg [rows,C], reg_label [rows,7] as [dx,dy,dz,h,w,l,ry], row_mask [rows] uint8 (the rows that take part: the
+ * reference's `[fg_mask]` selection), loss_mask [rows] uint8 or null, anchor [3] or [rows,3].
+ * opt and cst are HOST arrays.  opt [8] int32: per_loc_bin_num, loc_y_bin_num, num_head_bin, get_xz_fine, get_y_by_bin, get_ry_fine, anchor
+ * per row, 0.  cst [17] fp32, the reference's Python doubles rounded by the caller: loc_scope, 2 loc_scope - 1e-3, loc_bin_size,
+ * loc_bin_size / 2, the same four for y, angle_per_class, angle_per_class / 2, 2 pi, pi, pi * 0.5, pi * 1.5, pi * 0.25, 1e-3, pi * 0.5 - 1e-3.
+ * C = per_loc_bin_num * (xz_fine ? 4 : 2) + (y_by_bin ? 2 * loc_y_bin_num : 1) + 2 * num_head_bin + 3 <= 128, every bin count <= 64; else -3.
+ *
+ * drc_bin_reg_targets: bins [rows,4] int32 <- x, z, y (-1 when y is not binned), ry bin labels; res [rows,7] <- the normalised residual
+ *   labels x, z, y (the y offset itself when not binned), ry, and the three size residuals.  The code path of the loss.
+ * drc_bin_reg_loss_fwd: sums [16] fp64 (kept for the backward) and terms [16] fp32 <- 0 x_bin, 1 z_bin, 2 x_res, 3 z_res, 4 y_offset or
+ *   y_bin, 5 y_res, 6 ry_bin, 7 ry_res, 8 size, 9 loss_loc, 10 loss_angle, 11 loss_size, 12 selected rows, 13 selected rows with loss_mask.
+ *   With a loss_mask every term is sum / mask count (the size term too: not divided by 3), without one the mean (size over 3 rows); the
+ *   binned y terms are plain means in both cases; a zero count divides by nothing.
+ * drc_bin_reg_loss_bwd: grad_pred [rows,C] <- d (g_loc loss_loc + g_angle loss_angle + g_size loss_size) / d pred_reg, zero on unselected
+ *   rows; g_* are device scalars (null: 0).  Every element is written. */
+int drc_bin_reg_targets(int64_t rows, int C, const float* reg_label, const float* anchor, const int32_t* opt, const float* cst,
+                        int32_t* bins, float* res, void* stream);
+int drc_bin_reg_loss_fwd(int64_t rows, int C, const float* pred_reg, const float* reg_label, const uint8_t* row_mask,
+                         const uint8_t* loss_mask, const float* anchor, const int32_t* opt, const float* cst, double* sums, float* terms,
+                         double* scratch, void* stream);
+int drc_bin_reg_loss_bwd(int64_t rows, int C, const float* pred_reg, const float* reg_label, const uint8_t* row_mask,
+                         const uint8_t* loss_mask, const float* anchor, const int32_t* opt, const float* cst, const double* sums,
+                         const float* g_loc, const float* g_angle, const float* g_size, float* grad_pred, void* stream);
+/* The point classification losses over logits [n], labels [n] fp32 (1 foreground, 0 background, -1 ignored), mask [n] uint8 or null.
+ *   kind 1 BinaryCrossEntropy: weight fg_weight on foreground, sum over (label >= 0 and mask) / clamp(their count, 1); in the stable
+ *          form max(x,0) - x t + log1p(exp(-|x|)), gradient w (sigmoid(x) - t) / count (no clamp of log(1 - p) at 100)
+ *   kind 2 SigmoidFocalLoss (alpha, gamma): weights (pos + neg) / clamp(pos count, 1) over the masked rows
+ *   kind 3 DiceLoss: 1 - sum min(p, t) / clamp(sum max(p, t), 1) over label != ignore_target (pass mask = null: the reference has none)
+ * sums [16] fp64 (kept for the backward), terms [8] fp32 <- 0 loss, 1 / 2 its positive and negative parts (focal), 3 the normaliser before
+ * the clamp.  bwd: grad_logits [n] <- grad_out[0] * d loss / d logits, every element written. */
+int drc_point_cls_loss_fwd(int64_t n, int kind, const float* logits, const float* labels, const uint8_t* mask, float fg_weight, float alpha,
+                           float gamma, float ignore_target, double* sums, float* terms, double* scratch, void* stream);
+int drc_point_cls_loss_bwd(int64_t n, int kind, const float* logits, const float* labels, const uint8_t* mask, float fg_weight, float alpha,
+                           float gamma, float ignore_target, const double* sums, const float* grad_out, float* grad_logits, void* stream);
+
+/* SigmoidFocalClassificationLoss.forward, unreduced, over n elements: with grad_out null, out[i] <- (1 - p_t)^gamma alpha_t ce(x, t) w[i]
+ * (targets t in [0, 1], weights w); with grad_out [n], out[i] <- grad_out[i] * d that / d logits[i]. */
+int drc_focal_elementwise(int64_t n, const float* logits, const float* targets, const float* weights, float alpha, float gamma,
+                          const float* grad_out, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * The frame change between the two networks (pts/frame_ops.hip; point_rcnn.py:296-312): the RPN's outputs, in the centred and rotated
  * frame of each instance cloud, back to the rectified camera frame.  One launch:
  *   xyz [B,N,3], boxes [B,M,7] as [x,y,z,h,w,l,ry], mean [B,3] fp32, rot [B] fp64 (the angle InstancePointCloud rotated the cloud by)
