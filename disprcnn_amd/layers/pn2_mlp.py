@@ -5,14 +5,25 @@
 
 A layer is a pair (W [Cout,Cin], b [Cout]) with BatchNorm already folded in (`fold_bn`), or a `Packed` pair made once by `pack`: the
 kernels read weights K-major, so a raw pair is transposed on the device at every call and a packed one is not.  GPU tensors, fp32,
-inference only (no autograd); there is no torch fallback.  `sa_mlp_max_unfused` is the same arithmetic done the long way
+no autograd; there is no torch fallback.  `sa_mlp_max_unfused` is the same arithmetic done the long way
 (grouping_operation -> conv2d -> max) for tools/bench_rpn.py and the tests to compare against; the modules never call it.
+
+Training forms (autograd, on the backward kernels of pts/pn2_mlp_bwd.hip; layers without BatchNorm only):
+
+    pointwise_mlp_train(in0, in1, weight, bias, relu)        one layer; gradients for in0, in1, weight (its own shape) and bias
+    group_max(x)                                             (B,C,M,ns) -> (B,C,M), the max over ns; ties go to the lowest sample
+    sa_mlp_max_train(xyz, new_xyz, feats, idx, layers)       group -> subtract the centre -> layers -> group_max, all in HBM
+
+The weight gradient is summed in fp32 within a chunk of `WGRAD_CHUNK` columns and in fp64 across chunks, in chunk order: bit-identical
+run to run, and its bits depend on WGRAD_CHUNK.
 """
 import torch
 import torch.nn.functional as F
 
 from .. import engine as E
 from ..pts import _lib
+
+WGRAD_CHUNK = 2048          # pts/pn2_mlp_bwd.hip:kWgradChunk (checked against the library when it is first used)
 
 
 class Packed:
@@ -147,3 +158,184 @@ def sa_mlp_max_unfused(xyz, new_xyz, feats, idx, layers):
         w, b = (l.wt.t(), l.bias) if isinstance(l, Packed) else (l[0].reshape(l[0].shape[0], -1), l[1])
         g = F.relu(F.conv2d(g, w.reshape(w.shape[0], w.shape[1], 1, 1).contiguous(), b))
     return g.max(dim=3)[0]
+
+
+# ---- training forms
+def _check_chunk():
+    got = _lib.lib().drc_pn2_wgrad_chunk()
+    if got != WGRAD_CHUNK:
+        raise RuntimeError(f"pn2_mlp: the library was built with a weight-gradient chunk of {got}, this module expects {WGRAD_CHUNK}")
+
+
+def _dgrad(gout, out, w2, C0, C1, relu):
+    B, cout, N = gout.shape
+    gin = torch.empty((B, C0 + C1, N), dtype=torch.float32, device=gout.device)
+    st = _lib.lib().drc_pn2_pointwise_mlp_dgrad(B, N, C0, C1, cout, 1 if relu else 0, E._ptr(gout), E._ptr(out if relu else None), E._ptr(w2),
+                                                E._ptr(gin), E._stream_ptr(gout.device))
+    _lib.check(st, "drc_pn2_pointwise_mlp_dgrad")
+    return gin
+
+
+def _wgrad(gout, out, in0, in1, relu, want_w, want_b):
+    _check_chunk()
+    B, cout, N = gout.shape
+    C0, C1 = in0.shape[1], in1.shape[1] if in1 is not None else 0
+    n_ws = _lib.lib().drc_pn2_wgrad_workspace_floats(B, N, C0, C1, cout)
+    if n_ws < 0:
+        raise RuntimeError(f"drc_pn2_wgrad_workspace_floats failed: status {n_ws}")
+    ws = torch.empty(n_ws, dtype=torch.float32, device=gout.device)
+    gw = torch.empty((cout, C0 + C1), dtype=torch.float32, device=gout.device) if want_w else None
+    gb = torch.empty(cout, dtype=torch.float32, device=gout.device) if want_b else None
+    st = _lib.lib().drc_pn2_pointwise_mlp_wgrad(B, N, C0, C1, cout, 1 if relu else 0, E._ptr(gout), E._ptr(out if relu else None), E._ptr(in0),
+                                                E._ptr(in1), E._ptr(ws), E._ptr(gw), E._ptr(gb), E._stream_ptr(gout.device))
+    _lib.check(st, "drc_pn2_pointwise_mlp_wgrad")
+    return gw, gb
+
+
+class _PointwiseMlpTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, in0, in1, weight, bias, relu):
+        out = pointwise_mlp(in0, in1, weight, bias, relu)
+        ctx.relu = bool(relu)
+        ctx.save_for_backward(in0, in1, weight, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        in0, in1, weight, out = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        B, C0, N = in0.shape
+        C1 = in1.shape[1] if in1 is not None else 0
+        cout = weight.shape[0]
+        g0 = g1 = gw = gb = None
+        if B == 0 or N == 0:
+            g0 = torch.zeros_like(in0) if need[0] else None
+            g1 = torch.zeros_like(in1) if need[1] and in1 is not None else None
+            gw = torch.zeros_like(weight) if need[2] else None
+            gb = weight.new_zeros(cout) if need[3] else None
+            return g0, g1, gw, gb, None
+        E.require_gpu(gout, "pointwise_mlp_train (backward)")
+        gout = gout.contiguous()
+        in0c = in0.contiguous()
+        in1c = in1.contiguous() if C1 else None
+        if need[0] or (need[1] and C1):
+            gin = _dgrad(gout, out, weight.detach().reshape(cout, -1).contiguous(), C0, C1, ctx.relu)
+            if need[0]:
+                g0 = gin[:, :C0]
+            if need[1] and in1 is not None:
+                g1 = gin[:, C0:]
+        elif need[1] and in1 is not None:
+            g1 = torch.zeros_like(in1)
+        if need[2] or need[3]:
+            gw, gb = _wgrad(gout, out, in0c, in1c, ctx.relu, need[2], need[3])
+            if gw is not None:
+                gw = gw.reshape(weight.shape)
+        return g0, g1, gw, gb, None
+
+
+def pointwise_mlp_train(in0, in1, weight, bias, relu):
+    """pointwise_mlp with autograd: in0 (B,C0,N), in1 (B,C1,N) or None, weight [Cout,C0+C1] / [Cout,Cin,1] / [Cout,Cin,1,1], bias [Cout]
+    -> act(W . concat(in0, in1) + b) (B,Cout,N).  The backward gives gradients for in0, in1, weight (in weight's shape) and bias, each only
+    when it is needed."""
+    what = "pointwise_mlp_train"
+    E.require_gpu(in0, what)
+    if in1 is not None:
+        E.require_gpu(in1, what)
+        if in1.dim() == 3 and in1.shape[1] == 0:
+            in1 = None
+    if isinstance(weight, Packed):
+        raise RuntimeError(f"{what}: takes the raw conv weight, not a Packed")
+    E.require_gpu(weight, what)
+    if bias is None:
+        raise RuntimeError(f"{what}: the layer needs a bias")
+    E.require_gpu(bias, what)
+    return _PointwiseMlpTrain.apply(in0, in1, weight, bias, bool(relu))
+
+
+class _GroupMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        B, C, M, ns = x.shape
+        out = torch.empty((B, C, M), dtype=torch.float32, device=x.device)
+        arg = torch.empty((B, C, M), dtype=torch.int32, device=x.device)
+        rows = B * C * M
+        if rows:
+            st = _lib.lib().drc_pn2_group_max_fwd(rows, ns, E._ptr(x), E._ptr(out), E._ptr(arg), E._stream_ptr(x.device))
+            _lib.check(st, "drc_pn2_group_max_fwd")
+        ctx.ns = ns
+        ctx.save_for_backward(arg)
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, gout, _garg):
+        (arg,) = ctx.saved_tensors
+        B, C, M = arg.shape
+        gin = torch.empty((B, C, M, ctx.ns), dtype=torch.float32, device=arg.device)
+        rows = B * C * M
+        if rows:
+            E.require_gpu(gout, "group_max (backward)")
+            st = _lib.lib().drc_pn2_group_max_bwd(rows, ctx.ns, E._ptr(gout.contiguous()), E._ptr(arg), E._ptr(gin), E._stream_ptr(arg.device))
+            _lib.check(st, "drc_pn2_group_max_bwd")
+        return gin
+
+
+def group_max(x, return_arg=False):
+    """x (B,C,M,ns), 1 <= ns <= 64 -> the max over ns (B,C,M), with autograd: the whole gradient goes to the winner, the lowest sample
+    index among equal maxima.  return_arg: -> (out, arg int32 (B,C,M))."""
+    what = "group_max"
+    E.require_gpu(x, what)
+    if x.dim() != 4 or not 1 <= x.shape[3] <= 64:
+        raise RuntimeError(f"{what}: x must be [B,C,M,ns] with ns in 1..64, got {tuple(x.shape)}")
+    out, arg = _GroupMax.apply(x.contiguous())
+    return (out, arg) if return_arg else out
+
+
+def sa_mlp_max_train(xyz, new_xyz, feats, idx, layers):
+    """The training form of sa_mlp_max, with autograd through feats and the layers' parameters: xyz (B,N,3), new_xyz (B,M,3), feats (B,C,N)
+    or None, idx (B,M,ns) int32, layers: 1..3 of (weight, bias) raw parameters, ReLU after every layer -> (B, Cout, M).  The grouped
+    tensor and every layer's activation live in HBM: group (grouping_operation) -> subtract the centre -> pointwise_mlp_train over the
+    M * ns columns -> group_max.  The coordinates are constants of the graph."""
+    from .pointnet2 import grouping_operation
+    what = "sa_mlp_max_train"
+    E.require_gpu(xyz, what)
+    E.require_gpu(new_xyz, what)
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or new_xyz.dim() != 3 or new_xyz.shape[2] != 3 or new_xyz.shape[0] != xyz.shape[0]:
+        raise RuntimeError(f"{what}: xyz [B,N,3] and new_xyz [B,M,3] expected, got {tuple(xyz.shape)} and {tuple(new_xyz.shape)}")
+    B, N, _ = xyz.shape
+    M = new_xyz.shape[1]
+    C = 0
+    if feats is not None:
+        E.require_gpu(feats, what)
+        if feats.dim() != 3 or feats.shape[0] != B or feats.shape[2] != N:
+            raise RuntimeError(f"{what}: feats must be [{B},C,{N}], got {tuple(feats.shape)}")
+        C = feats.shape[1]
+    if not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 3 or idx.shape[:2] != (B, M):
+        raise RuntimeError(f"{what}: idx must be an int32 GPU tensor [{B},{M},ns], got {idx.dtype} {tuple(idx.shape)}")
+    ns = idx.shape[2]
+    if not 1 <= ns <= 64:
+        raise RuntimeError(f"{what}: nsample must be in 1..64, got {ns}")
+    layers = list(layers)
+    if not 1 <= len(layers) <= 3:
+        raise RuntimeError(f"{what}: 1 to 3 layers, got {len(layers)}")
+    cin = C + 3
+    for i, (w, b) in enumerate(layers):
+        if w.shape[0] < 1 or w.numel() != w.shape[0] * cin:
+            raise RuntimeError(f"{what}: layer {i} has weight {tuple(w.shape)}, its input has {cin} channels")
+        cin = w.shape[0]
+    if B == 0 or M == 0:
+        # nothing to launch: a correctly shaped result that still hangs on its inputs, so that backward gives them zero gradients
+        out = torch.zeros((B, cin, M), dtype=torch.float32, device=xyz.device)
+        for t in [feats] + [p for l in layers for p in l]:
+            if t is not None and t.requires_grad:
+                out = out + 0.0 * t.sum()
+        return out
+    idx = idx.contiguous()
+    with torch.no_grad():
+        g = grouping_operation(xyz.detach().transpose(1, 2).contiguous(), idx) - new_xyz.detach().transpose(1, 2).unsqueeze(-1)
+    if C:
+        g = torch.cat([g, grouping_operation(feats.contiguous(), idx)], dim=1)
+    x = g.reshape(B, C + 3, M * ns)
+    for w, b in layers:
+        x = pointwise_mlp_train(x, None, w, b, True)
+    return group_max(x.reshape(B, cin, M, ns))

@@ -1,4 +1,5 @@
-"""RCNNNet: the second network of PointRCNN's 3D stage (reference: point_rcnn/lib/net/rcnn_net.py), evaluation forward on HIP.
+"""RCNNNet: the second network of PointRCNN's 3D stage (reference: point_rcnn/lib/net/rcnn_net.py) on HIP: the evaluation forward, and
+the training step on already sampled ROIs.
 
 RPN output -> per ROI: the points inside the enlarged proposal in its canonical frame ++ mask ++ depth ++ RPN features (one fused
 pooling kernel, layers/roipool3d.roipool3d_canonical) -> xyz_up / merge_down shared MLPs -> three single-scale SA levels, the last one
@@ -10,9 +11,16 @@ the 256-channel concat is not built either.  The heads see one column per ROI an
 weights are cached by the parameter holders (pytorch_utils).
 
 The state-dict keys equal the reference's for the same cfg (the Dropout at index 1 of each head keeps the indices), so a reference
-checkpoint loads with strict=True.  No loss, no ProposalTargetLayer, no backward: a forward in training mode raises.
+checkpoint loads with strict=True.
 
-    forward(proposals) -> (list of BoxList, {})      the reference's interface
+Training (RCNN.USE_BN = False; a BatchNorm layer in training raises): with RCNN.ROI_SAMPLE_JIT = False `proposals` carries the sampled
+ROIs (pts_input, roi_boxes3d, cls_label, reg_valid_mask, gt_boxes3d_ct), the network runs with autograd on the training forms of
+layers/pn2_mlp.py (the eval arithmetic with the raw weights, activations in HBM, HIP backward) and the loss is
+PointRCNNBox3dLossComputation.  With ROI_SAMPLE_JIT = True a training forward raises: ProposalTargetLayer is not built.  The
+coordinates are constants of the graph (FPS, ball query and the grouped coordinates carry no gradient).
+
+    forward(proposals) -> (list of BoxList, {})                       evaluation: the reference's interface
+    forward(proposals) -> (proposals, {'loss_box3d': loss})           training, ROI_SAMPLE_JIT = False
     refine(proposals)  -> (box (B,7) 'ry_lhwxyz', score (B), random (B))    what combine_2d_3d keeps of those lists; no host sync
 """
 import torch
@@ -25,6 +33,7 @@ from disprcnn_amd.layers.roipool3d import roipool3d_canonical
 from ..pointnet2_lib.pointnet2 import pytorch_utils as pt_utils
 from ..pointnet2_lib.pointnet2.pointnet2_modules import PointnetSAModule
 from .rcnn_inference import Box3DPointRCNNPostProcess
+from .rcnn_loss import PointRCNNBox3dLossComputation
 
 
 class RCNNNet(nn.Module):
@@ -71,6 +80,10 @@ class RCNNNet(nn.Module):
                                                         rcnn.LOC_Y_SCOPE, rcnn.LOC_Y_BIN_SIZE))
         self.init_weights()
         self.inference = Box3DPointRCNNPostProcess(cfg)
+        try:
+            self.loss = PointRCNNBox3dLossComputation(cfg)
+        except NotImplementedError:                        # a config the eval network accepts (LOSS_CLS = 'CrossEntropy'): raised again
+            self.loss = None                               # by the first training forward
 
     def init_weights(self):
         for m in self.modules():
@@ -80,10 +93,9 @@ class RCNNNet(nn.Module):
                     nn.init.constant_(m.bias, 0)
         nn.init.normal_(self.reg_layer[-1].conv.weight, mean=0, std=0.001)
 
-    @staticmethod
-    def _head(layers, x):
+    def _head(self, layers, x):
         for layer in layers:
-            if not isinstance(layer, nn.Dropout):          # evaluation: dropout is the identity
+            if self.training or not isinstance(layer, nn.Dropout):          # evaluation: dropout is the identity
                 x = layer(x)
         return x
 
@@ -108,11 +120,16 @@ class RCNNNet(nn.Module):
         levels = []
         if self.cfg.RCNN.USE_RPN_FEATURES:
             x = pts
-            for layer in self.xyz_up_layer:
-                x = pn2_mlp.pointwise_mlp(x, None, layer.folded(), None, layer.relu)
-            levels.append(x)
             merge = self.merge_down_layer[0]
-            features = pn2_mlp.pointwise_mlp(x, feat, merge.folded(), None, merge.relu)
+            if self.training:
+                for layer in self.xyz_up_layer:
+                    x = pn2_mlp.pointwise_mlp_train(x, None, *layer.train_layer(), layer.relu)
+                features = pn2_mlp.pointwise_mlp_train(x, feat, *merge.train_layer(), merge.relu)
+            else:
+                for layer in self.xyz_up_layer:
+                    x = pn2_mlp.pointwise_mlp(x, None, layer.folded(), None, layer.relu)
+                features = pn2_mlp.pointwise_mlp(x, feat, merge.folded(), None, merge.relu)
+            levels.append(x)
             levels.append(features)
         else:
             features = feat if feat.shape[1] else None
@@ -136,7 +153,17 @@ class RCNNNet(nn.Module):
 
     def forward(self, proposals, targets=None):
         if self.training:
-            raise NotImplementedError("RCNNNet: only the evaluation forward is implemented (no loss, no backward); call .eval()")
+            if self.cfg.RCNN.ROI_SAMPLE_JIT:               # before `proposals` is read
+                raise NotImplementedError("RCNNNet: training with RCNN.ROI_SAMPLE_JIT = True needs ProposalTargetLayer, which is not "
+                                          "implemented; sample the ROIs beforehand (ROI_SAMPLE_JIT = False) or call .eval()")
+            if self.loss is None:
+                self.loss = PointRCNNBox3dLossComputation(self.cfg)
+            target_dict = {"pts_input": proposals["pts_input"], "roi_boxes3d": proposals["roi_boxes3d"], "cls_label": proposals["cls_label"],
+                           "reg_valid_mask": proposals["reg_valid_mask"], "gt_of_rois": proposals["gt_boxes3d_ct"]}
+            with torch.enable_grad():
+                ret_dict = self.network(proposals)
+                loss_box3d = self.loss(ret_dict, proposals, target_dict, targets)
+            return proposals, dict(loss_box3d=loss_box3d)
         with torch.no_grad():
             ret_dict = self.network(proposals)
             return self.inference(ret_dict, proposals), {}
@@ -144,6 +171,6 @@ class RCNNNet(nn.Module):
     def refine(self, proposals):
         """-> (box (B,7) 'ry_lhwxyz', score (B), random (B)): the arg-max entry of each cloud's BoxList, without a host sync."""
         if self.training:
-            raise NotImplementedError("RCNNNet: only the evaluation forward is implemented (no loss, no backward); call .eval()")
+            raise NotImplementedError("RCNNNet.refine: evaluation only; call .eval()")
         with torch.no_grad():
             return self.inference.best(self.network(proposals), proposals)

@@ -1,5 +1,5 @@
-"""PointNet++ set-abstraction and feature-propagation modules (reference: pointnet2_lib/pointnet2/pointnet2_modules.py), inference
-only, on the HIP kernels: the index ops of layers/pointnet2.py and the fused shared MLPs of layers/pn2_mlp.py.
+"""PointNet++ set-abstraction and feature-propagation modules (reference: pointnet2_lib/pointnet2/pointnet2_modules.py) on the HIP
+kernels: the index ops of layers/pointnet2.py and the fused shared MLPs of layers/pn2_mlp.py.
 
 An SA module is FPS -> gather -> per scale: ball query -> one fused group / MLP / max kernel that writes its scale's channels into
 the module's output, so neither the grouped tensor nor a torch.cat exists.  With npoint=None (GroupAll, the RCNN's last level) the one
@@ -7,6 +7,10 @@ neighbourhood is the whole cloud: the same kernel with new_xyz = 0 (x - 0 is exa
 M = 1 and idx = 0..N-1; the cloud must fit one neighbourhood (N <= 64).  An FP module is three_nn -> weights -> three_interpolate
 -> the MLP, whose first layer reads the interpolated and the skip features as two inputs.  FPS and ball query read coordinates only,
 so every index equals the reference's.
+
+In training mode an SA module without BatchNorm takes the materialising route (pn2_mlp.sa_mlp_max_train per scale, torch.cat over the
+scales) with autograd through the features and the layers' parameters; FPS, gather and ball query stay under no_grad, so the
+coordinates are constants of the graph.  A BatchNorm layer in training, and PointnetFPModule in training, raise.
 """
 from typing import List
 
@@ -44,14 +48,19 @@ class PointnetSAModuleMSG(nn.Module):
 
     def forward(self, xyz, features=None, new_xyz=None):
         """xyz (B,N,3), features (B,C,N) or None -> new_xyz (B,npoint,3), new_features (B, sum of the scales' widths, npoint)."""
-        if self.training:
-            raise NotImplementedError("PointnetSAModuleMSG: the HIP forward is inference only; call .eval()")
+        train = [m.train_layers() for m in self.mlps] if self.training else None          # raises for a BatchNorm layer
         if self.npoint is None:
-            return None, self._forward_group_all(xyz, features)
+            return None, self._forward_group_all(xyz, features, train)
         with torch.no_grad():
             if new_xyz is None:
                 fps_idx = pointnet2_utils.furthest_point_sample(xyz, self.npoint)
                 new_xyz = pointnet2_utils.gather_operation(xyz.transpose(1, 2).contiguous(), fps_idx).transpose(1, 2).contiguous()
+            if train is not None:
+                idxs = [pointnet2_utils.ball_query(g.radius, g.nsample, xyz, new_xyz) for g in self.groupers]
+        if train is not None:
+            outs = [pn2_mlp.sa_mlp_max_train(xyz, new_xyz, features, idx, layers) for idx, layers in zip(idxs, train)]
+            return new_xyz, torch.cat(outs, dim=1)
+        with torch.no_grad():
             folded = [m.folded() for m in self.mlps]
             out = torch.empty((xyz.shape[0], sum(f[-1].cout for f in folded), new_xyz.shape[1]), dtype=torch.float32, device=xyz.device)
             c_off = 0
@@ -61,20 +70,23 @@ class PointnetSAModuleMSG(nn.Module):
                 c_off += layers[-1].cout
         return new_xyz, out
 
-    def _forward_group_all(self, xyz, features):
+    def _forward_group_all(self, xyz, features, train=None):
         """GroupAll: (B,N,3), (B,C,N) -> (B, sum of the widths, 1), the max over all N points of the MLP of raw xyz ++ features."""
         B, N = xyz.shape[0], xyz.shape[1]
         if not 1 <= N <= 64:
             raise NotImplementedError(f"PointnetSAModuleMSG with npoint=None: the fused kernel holds one neighbourhood of at most 64 points, "
                                       f"got {N}")
         with torch.no_grad():
-            folded = [m.folded() for m in self.mlps]
-            out = torch.empty((B, sum(f[-1].cout for f in folded), 1), dtype=torch.float32, device=xyz.device)
             key = (B, N, xyz.device)
             if getattr(self, "_group_all", (None,))[0] != key:      # constants of the shape: made once, not per call
                 self._group_all = (key, torch.zeros((B, 1, 3), dtype=torch.float32, device=xyz.device),
                                    torch.arange(N, dtype=torch.int32, device=xyz.device).view(1, 1, N).expand(B, 1, N).contiguous())
             _, origin, idx = self._group_all
+        if train is not None:
+            return torch.cat([pn2_mlp.sa_mlp_max_train(xyz, origin, features, idx, layers) for layers in train], dim=1)
+        with torch.no_grad():
+            folded = [m.folded() for m in self.mlps]
+            out = torch.empty((B, sum(f[-1].cout for f in folded), 1), dtype=torch.float32, device=xyz.device)
             c_off = 0
             for layers in folded:
                 pn2_mlp.sa_mlp_max(xyz, origin, features, idx, layers, out=out, c_off=c_off)

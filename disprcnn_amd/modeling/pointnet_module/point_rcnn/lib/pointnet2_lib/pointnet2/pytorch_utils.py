@@ -1,9 +1,12 @@
-"""Parameter holders of PointRCNN's shared MLPs (reference: pointnet2_lib/pointnet2/pytorch_utils.py), inference only.
+"""Parameter holders of PointRCNN's shared MLPs (reference: pointnet2_lib/pointnet2/pytorch_utils.py).
 
 `SharedMLP`, `Conv1d` and `Conv2d` keep the reference's submodule names (`layer<i>.conv`, `layer<i>.bn.bn`, `conv`, `bn.bn`), so a
 reference state dict loads with strict=True.  They do not run torch convolutions: `folded()` gives the layer as the HIP kernels of
 layers/pn2_mlp.py read it (BatchNorm folded in fp64 on the host, K-major on the device), cached and made again when a parameter or
 buffer changes.  Calling a holder directly does its one layer through `pointwise_mlp`.
+
+In training mode a layer without BatchNorm runs through `pn2_mlp.pointwise_mlp_train` with its raw parameters as autograd inputs (the
+eval arithmetic, plus the HIP backward); a layer with BatchNorm raises: batch statistics are not built.
 """
 import torch.nn as nn
 
@@ -69,13 +72,24 @@ class _ConvBase(nn.Module):
             self._fold = (key, pn2_mlp.pack(wf.to(w.device), bf.to(w.device)))
         return self._fold[1]
 
+    def train_layer(self):
+        """(weight, bias): the raw parameters, as the training forms of layers/pn2_mlp.py take them."""
+        if hasattr(self, "bn"):
+            raise NotImplementedError("BatchNorm in training mode: the HIP shared MLPs train without BatchNorm only (USE_BN = False)")
+        if self.conv.bias is None:
+            raise NotImplementedError("a layer without bias in training mode is not supported by the HIP shared-MLP kernels")
+        return self.conv.weight, self.conv.bias
+
     def forward(self, x):
         squeeze = x.dim() == 4
         if squeeze:
             if x.shape[3] != 1:
                 raise NotImplementedError("a shared MLP over grouped points runs through layers.pn2_mlp.sa_mlp_max")
             x = x.squeeze(3)
-        y = pn2_mlp.pointwise_mlp(x, None, self.folded(), None, self.relu)
+        if self.training:
+            y = pn2_mlp.pointwise_mlp_train(x, None, *self.train_layer(), self.relu)
+        else:
+            y = pn2_mlp.pointwise_mlp(x, None, self.folded(), None, self.relu)
         return y.unsqueeze(3) if squeeze else y
 
 
@@ -98,3 +112,6 @@ class SharedMLP(nn.Sequential):
 
     def folded(self):
         return [layer.folded() for layer in self]
+
+    def train_layers(self):
+        return [layer.train_layer() for layer in self]

@@ -36,6 +36,12 @@ _SIGS = {
     "drc_pts_in_boxes3d": (_I, [_I, _I, _I, _P, _P, _P, _P]),
     "drc_pn2_sa_mlp_max_fwd": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P]),
     "drc_pn2_pointwise_mlp_fwd": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _I, _I, _P]),
+    "drc_pn2_pointwise_mlp_dgrad": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "drc_pn2_wgrad_chunk": (_I, []),
+    "drc_pn2_wgrad_workspace_floats": (_L, [_I, _I, _I, _I, _I]),
+    "drc_pn2_pointwise_mlp_wgrad": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "drc_pn2_group_max_fwd": (_I, [_L, _I, _P, _P, _P, _P]),
+    "drc_pn2_group_max_bwd": (_I, [_L, _I, _P, _P, _P, _P]),
     "drc_rpn_points_depth": (_I, [_L, _P, _P, _P]),
     "drc_rpn_decode_proposals": (_I, [_L, _I, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
     "drc_rcnn_pool_canonical_fwd": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _F, _F, _P, _P, _P, _P, _P]),

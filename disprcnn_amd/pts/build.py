@@ -13,7 +13,7 @@ from ..csrc.build import FLAGS, HIPCC
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["points.hip", "pointnet2.hip", "boxes3d.hip", "pn2_mlp.hip", "rcnn_ops.hip", "frame_ops.hip", "kitti_eval.hip",
-           "train_targets.hip"]
+           "train_targets.hip", "pn2_mlp_bwd.hip"]
 HEADER = os.path.join(HERE, "..", "..", "include", "disprcnn_pts.h")
 SHARED = os.path.join(HERE, "box3d_pt.h")                 # included by boxes3d.hip and rcnn_ops.hip
 LIB = os.path.join(HERE, "libdisprcnn_pts.so")

@@ -128,6 +128,30 @@ int drc_rpn_decode_proposals(int64_t n, int R, const float* xyz, const float* re
 int drc_rpn_points_depth(int64_t n, const float* xyz, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Backward of the shared MLPs (pts/pn2_mlp_bwd.hip): one pointwise layer out = act(W . concat(in0, in1) + b) with the conv weight in its
+ * OWN layout W [Cout, Cin] (Cin = C0 + C1), and the max over a neighbourhood with its winner.  fp32, [B, C, N] channel-major.  With
+ * gZ = gout (.) [out > 0] when relu != 0 (out: the layer's output, may be null otherwise), gZ = gout when relu == 0; the mask is applied
+ * while the operand is loaded.  No atomics, no allocation, no synchronisation; -1 bad arguments, -2 limits (B <= 65535).
+ * ------------------------------------------------------------------------------------- */
+/* gin [B, C0 + C1, N] <- W^T . gZ on fp32 MFMA; the two inputs' gradients are its channel ranges.  Every element is written. */
+int drc_pn2_pointwise_mlp_dgrad(int B, int N, int C0, int C1, int cout, int relu, const float* gout, const float* out, const float* w,
+                                float* gin, void* stream);
+/* The number of columns of the flattened (b, n) axis one partial sum covers. */
+int drc_pn2_wgrad_chunk(void);
+/* Floats of workspace drc_pn2_pointwise_mlp_wgrad needs: ceil(B N / chunk) * Cout * (Cin + 1); -1 for bad arguments. */
+int64_t drc_pn2_wgrad_workspace_floats(int B, int N, int C0, int C1, int cout);
+/* gw [Cout, Cin] <- sum_{b,n} gZ[b, co, n] X[b, ci, n], gb [Cout] <- sum_{b,n} gZ[b, co, n] (either may be null, not both).  Split over the
+ * columns: fp32 MFMA partials per chunk into `workspace` (contents need not be set), then added in fp64 in chunk order and rounded once:
+ * the same bits run to run, which depend on the chunk length. */
+int drc_pn2_pointwise_mlp_wgrad(int B, int N, int C0, int C1, int cout, int relu, const float* gout, const float* out, const float* in0,
+                                const float* in1, float* workspace, float* gw, float* gb, void* stream);
+/* x [rows, ns] (rows = B C M) -> out [rows] = max over ns, arg [rows] int32 (may be null) = the winner's sample, ties to the lowest index.
+ * 1 <= ns <= 64. */
+int drc_pn2_group_max_fwd(int64_t rows, int ns, const float* x, float* out, int32_t* arg, void* stream);
+/* gin [rows, ns] <- gout [rows] at arg [rows], zero elsewhere; every element is written. */
+int drc_pn2_group_max_bwd(int64_t rows, int ns, const float* gout, const int32_t* arg, float* gin, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * PointRCNN RCNN stage (pts/rcnn_ops.hip; rcnn_net.py's ROI_SAMPLE_JIT eval branch, rcnn_inference.py).
  * ------------------------------------------------------------------------------------- */
 /* ROI pooling fused with the canonical transform, one workgroup per (cloud, ROI), in the layouts the RPN returns and the shared MLPs
