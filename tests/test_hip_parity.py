@@ -67,6 +67,7 @@ def test_cost_volume_blocked_matches_dense(dev):
 
 
 def test_cost_volume_backward_is_adjoint(dev):
+    """drc_cost_volume_bwd against the oracle's autograd (one shape; edge shapes in `test_hip_train_adjoints.py`)."""
     from disprcnn_amd import ops
     fl, fr = synth.synth_features(2, 4, 6, 20, tag="adj")
     g = synth.hash_uniform("adj:g", (2, 8, 6, 6, 20))

@@ -260,7 +260,8 @@ def test_wgrad_partial_sums_vs_atomic_flush_and_oracle(dev, n, cin, cout, dims, 
 def test_spp_adjoints(dev):
     """drc_bilinear_up_blocked_bwd / drc_avgpool2d_blocked_bwd are the exact adjoints of the forward SPP kernels
     (reference: autograd of F.interpolate(bilinear, align_corners=True) and AvgPool2d, submodule.py:76-96,128-137):
-    <fwd(x), g> == <x, bwd(g)> to fp32 rounding, at the real branch sizes (56x56 map, pools 8/16/32... -> 7/3/1)."""
+    <fwd(x), g> == <x, bwd(g)> to fp32 rounding, at the real branch sizes (56x56 map, pools 8/16/32... -> 7/3/1)
+    (one shape; edge shapes in `test_hip_train_adjoints.py`)."""
     from disprcnn_amd import _lib, engine as E
     lib, sp = _lib.lib(), E._stream_ptr(dev)
     n, H4, W4 = 2, 56, 72
