@@ -16,11 +16,15 @@ checkpoint loads with strict=True.
 Training (RCNN.USE_BN = False; a BatchNorm layer in training raises): with RCNN.ROI_SAMPLE_JIT = False `proposals` carries the sampled
 ROIs (pts_input, roi_boxes3d, cls_label, reg_valid_mask, gt_boxes3d_ct), the network runs with autograd on the training forms of
 layers/pn2_mlp.py (the eval arithmetic with the raw weights, activations in HBM, HIP backward) and the loss is
-PointRCNNBox3dLossComputation.  With ROI_SAMPLE_JIT = True a training forward raises: ProposalTargetLayer is not built.  The
-coordinates are constants of the graph (FPS, ball query and the grouped coordinates carry no gradient).
+PointRCNNBox3dLossComputation.  With ROI_SAMPLE_JIT = True (the reference's real step) `targets` carries each cloud's ground-truth box:
+ProposalTargetLayer samples, pools and labels the ROIs under no_grad (rpn/proposal_target_layer.py; its random draws may be passed as
+proposals['draws'], else they come from torch's default generator), then the same network and loss run on them.  Without `targets` that
+path raises NotImplementedError.  The coordinates are constants of the graph (FPS, ball query and the grouped coordinates carry no
+gradient).
 
     forward(proposals) -> (list of BoxList, {})                       evaluation: the reference's interface
     forward(proposals) -> (proposals, {'loss_box3d': loss})           training, ROI_SAMPLE_JIT = False
+    forward(proposals, targets) -> (proposals, {'loss_box3d': loss})  training, ROI_SAMPLE_JIT = True
     refine(proposals)  -> (box (B,7) 'ry_lhwxyz', score (B), random (B))    what combine_2d_3d keeps of those lists; no host sync
 """
 import torch
@@ -32,6 +36,7 @@ from disprcnn_amd.layers.roipool3d import roipool3d_canonical
 
 from ..pointnet2_lib.pointnet2 import pytorch_utils as pt_utils
 from ..pointnet2_lib.pointnet2.pointnet2_modules import PointnetSAModule
+from ..rpn.proposal_target_layer import ProposalTargetLayer
 from .rcnn_inference import Box3DPointRCNNPostProcess
 from .rcnn_loss import PointRCNNBox3dLossComputation
 
@@ -78,6 +83,7 @@ class RCNNNet(nn.Module):
         self.cls_layer = head(rcnn.CLS_FC, 1)
         self.reg_layer = head(rcnn.REG_FC, reg_channels(rcnn.LOC_SCOPE, rcnn.LOC_BIN_SIZE, rcnn.NUM_HEAD_BIN, rcnn.LOC_Y_BY_BIN,
                                                         rcnn.LOC_Y_SCOPE, rcnn.LOC_Y_BIN_SIZE))
+        self.proposal_target_layer = ProposalTargetLayer(cfg, total_cfg)        # no parameters: the state dict is the reference's
         self.init_weights()
         self.inference = Box3DPointRCNNPostProcess(cfg)
         try:
@@ -138,9 +144,9 @@ class RCNNNet(nn.Module):
             levels.append(features)
         return levels
 
-    def network(self, proposals):
-        """-> {'rcnn_cls': (R,1), 'rcnn_reg': (R, reg channels)}, R = B * M"""
-        xyz, pts, feat = self.pool(proposals)
+    def network(self, proposals, pooled=None):
+        """-> {'rcnn_cls': (R,1), 'rcnn_reg': (R, reg channels)}, R = B * M; pooled: (xyz, pts, feat) when ProposalTargetLayer made them"""
+        xyz, pts, feat = self.pool(proposals) if pooled is None else pooled
         R = xyz.shape[0]
         if R == 0:
             n_reg = self.reg_layer[-1].conv.weight.shape[0]
@@ -151,17 +157,32 @@ class RCNNNet(nn.Module):
         rcnn_reg = self._head(self.reg_layer, cols)[0].t().contiguous()          # (R, reg channels)
         return {"rcnn_cls": rcnn_cls, "rcnn_reg": rcnn_reg}
 
+    @staticmethod
+    def get_box3d_batch(boxlist):
+        return torch.cat([t.get_field("box3d").convert("xyzhwl_ry").bbox_3d for t in boxlist])
+
     def forward(self, proposals, targets=None):
         if self.training:
-            if self.cfg.RCNN.ROI_SAMPLE_JIT:               # before `proposals` is read
-                raise NotImplementedError("RCNNNet: training with RCNN.ROI_SAMPLE_JIT = True needs ProposalTargetLayer, which is not "
-                                          "implemented; sample the ROIs beforehand (ROI_SAMPLE_JIT = False) or call .eval()")
+            if self.cfg.RCNN.ROI_SAMPLE_JIT and targets is None:               # before `proposals` is read
+                raise NotImplementedError("RCNNNet: training with RCNN.ROI_SAMPLE_JIT = True samples its ROIs with ProposalTargetLayer, which "
+                                          "needs the ground-truth boxes: pass `targets`, or sample the ROIs beforehand (ROI_SAMPLE_JIT = "
+                                          "False), or call .eval()")
             if self.loss is None:
                 self.loss = PointRCNNBox3dLossComputation(self.cfg)
-            target_dict = {"pts_input": proposals["pts_input"], "roi_boxes3d": proposals["roi_boxes3d"], "cls_label": proposals["cls_label"],
-                           "reg_valid_mask": proposals["reg_valid_mask"], "gt_of_rois": proposals["gt_boxes3d_ct"]}
+            pooled = None
+            if self.cfg.RCNN.ROI_SAMPLE_JIT:
+                with torch.no_grad():
+                    gt = self.get_box3d_batch(targets).unsqueeze(1)
+                    t = self.proposal_target_layer.sample(proposals, gt, draws=proposals.get("draws"))
+                pooled = (t["xyz"], t["pts"], t["feat"])
+                # the loss reads pts_input's row count only: the point-major tensor is not built
+                target_dict = {"pts_input": t["xyz"], "roi_boxes3d": t["roi_boxes3d"], "cls_label": t["cls_label"],
+                               "reg_valid_mask": t["reg_valid_mask"], "gt_of_rois": t["gt_of_rois"]}
+            else:
+                target_dict = {"pts_input": proposals["pts_input"], "roi_boxes3d": proposals["roi_boxes3d"], "cls_label": proposals["cls_label"],
+                               "reg_valid_mask": proposals["reg_valid_mask"], "gt_of_rois": proposals["gt_boxes3d_ct"]}
             with torch.enable_grad():
-                ret_dict = self.network(proposals)
+                ret_dict = self.network(proposals, pooled)
                 loss_box3d = self.loss(ret_dict, proposals, target_dict, targets)
             return proposals, dict(loss_box3d=loss_box3d)
         with torch.no_grad():

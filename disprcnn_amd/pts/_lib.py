@@ -46,6 +46,11 @@ _SIGS = {
     "drc_rpn_decode_proposals": (_I, [_L, _I, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
     "drc_rcnn_pool_canonical_fwd": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _F, _F, _P, _P, _P, _P, _P]),
     "drc_rcnn_decode_boxes": (_I, [_L, _I, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P]),
+    "drc_rcnn_sample_max_candidates": (_I, []),
+    "drc_rcnn_sample_max_slots": (_I, []),
+    "drc_rcnn_sample_rois": (_I, [_I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _D, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
+    "drc_rcnn_pool_target_fwd": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P,
+                                      _P, _P, _P, _P, _P]),
     "drc_rpn_to_camera_fwd": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "drc_train_scratch_doubles": (_I, []),
     "drc_rpn_point_labels": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P]),

@@ -1,5 +1,5 @@
-// box3d_pt.h -- the pieces of roipool3d that boxes3d.hip and rcnn_ops.hip share: pt_in_box3d in its mixed precision and the selection of
-// the first S in-box points of one (cloud, box) by one workgroup.
+// box3d_pt.h -- the pieces of roipool3d that boxes3d.hip, rcnn_ops.hip and proposal_target.hip share: pt_in_box3d in its mixed precision,
+// the selection of the first S in-box points of one (cloud, box) by one workgroup, and the channel-major row gather of the pooled outputs.
 //
 //   reference: point_rcnn/lib/utils/roipool3d/src/roipool3d_kernel.cu (pt_in_box3d, get_pooled_idx)
 #ifndef DISPRCNN_BOX3D_PT_H
@@ -51,6 +51,31 @@ __device__ __forceinline__ int select_in_box(int N, int S, const float* __restri
         __syncthreads();
     }
     return cnt;
+}
+
+// rows along S: out[c * S + s] = src[c * N + sidx[s]] (src null: zeros), waves take the channels in turn
+__device__ __forceinline__ void gather_rows(int C, int N, int S, const float* __restrict__ src, const int32_t* sidx, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((S & 3) == 0) {
+        for (int c = wave; c < C; c += kPoolThreads / 64) {
+            const float* row = src ? src + (int64_t)c * N : nullptr;
+            float* o = out + (int64_t)c * S;
+            for (int s = lane * 4; s < S; s += 256) {
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (row) {
+                    const int4 i = *reinterpret_cast<const int4*>(sidx + s);
+                    v = make_float4(row[i.x], row[i.y], row[i.z], row[i.w]);
+                }
+                *reinterpret_cast<float4*>(o + s) = v;
+            }
+        }
+    } else {
+        for (int c = wave; c < C; c += kPoolThreads / 64) {
+            const float* row = src ? src + (int64_t)c * N : nullptr;
+            float* o = out + (int64_t)c * S;
+            for (int s = lane; s < S; s += 64) o[s] = row ? row[sidx[s]] : 0.f;
+        }
+    }
 }
 
 }  // namespace box3d_pt

@@ -13,9 +13,9 @@ from ..csrc.build import FLAGS, HIPCC
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["points.hip", "pointnet2.hip", "boxes3d.hip", "pn2_mlp.hip", "rcnn_ops.hip", "frame_ops.hip", "kitti_eval.hip",
-           "train_targets.hip", "pn2_mlp_bwd.hip"]
+           "train_targets.hip", "pn2_mlp_bwd.hip", "proposal_target.hip"]
 HEADER = os.path.join(HERE, "..", "..", "include", "disprcnn_pts.h")
-SHARED = os.path.join(HERE, "box3d_pt.h")                 # included by boxes3d.hip and rcnn_ops.hip
+SHARED = [os.path.join(HERE, h) for h in ("box3d_pt.h", "box3d_iou.h")]     # included by boxes3d.hip, rcnn_ops.hip, proposal_target.hip
 LIB = os.path.join(HERE, "libdisprcnn_pts.so")
 MAX_JOBS = 16
 
@@ -28,7 +28,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(d) > t for d in _sources() + [HEADER, SHARED, __file__])
+    return any(os.path.getmtime(d) > t for d in _sources() + [HEADER, __file__] + SHARED)
 
 
 def build(force=False, verbose=True):
@@ -37,7 +37,7 @@ def build(force=False, verbose=True):
     objs, jobs = [], []
     for src in _sources():
         obj = src[:-4] + ".o"
-        if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(d) for d in [src, HEADER, SHARED]):
+        if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(d) for d in [src, HEADER] + SHARED):
             jobs.append([HIPCC] + FLAGS + ["-c", src, "-o", obj])
         objs.append(obj)
     if jobs:

@@ -21,31 +21,7 @@ namespace {
 
 using box3d_pt::kMaxPoolSamples;
 using box3d_pt::kPoolThreads;
-
-// rows along S: out[c * S + s] = src[c * N + sidx[s]] (src null: zeros), waves take the channels in turn
-__device__ __forceinline__ void gather_rows(int C, int N, int S, const float* __restrict__ src, const int32_t* sidx, float* __restrict__ out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if ((S & 3) == 0) {
-        for (int c = wave; c < C; c += kPoolThreads / 64) {
-            const float* row = src ? src + (int64_t)c * N : nullptr;
-            float* o = out + (int64_t)c * S;
-            for (int s = lane * 4; s < S; s += 256) {
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (row) {
-                    const int4 i = *reinterpret_cast<const int4*>(sidx + s);
-                    v = make_float4(row[i.x], row[i.y], row[i.z], row[i.w]);
-                }
-                *reinterpret_cast<float4*>(o + s) = v;
-            }
-        }
-    } else {
-        for (int c = wave; c < C; c += kPoolThreads / 64) {
-            const float* row = src ? src + (int64_t)c * N : nullptr;
-            float* o = out + (int64_t)c * S;
-            for (int s = lane; s < S; s += 64) o[s] = row ? row[sidx[s]] : 0.f;
-        }
-    }
-}
+using box3d_pt::gather_rows;             // shared with proposal_target.hip
 
 __global__ __launch_bounds__(kPoolThreads) void pool_canonical_kernel(int N, int M, int C, int S, int E, const float* __restrict__ xyz,
                                                                       const float* __restrict__ feat, const float* __restrict__ mask,

@@ -178,6 +178,46 @@ int drc_rcnn_decode_boxes(int64_t n, int R, const float* rois, const float* reg,
                           float anchor_w, float anchor_l, float* boxes, float* bev, float* norm_score, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * PointRCNN's ProposalTargetLayer (pts/proposal_target.hip; rpn/proposal_target_layer.py): the RCNN stage's training ROIs.  Neither
+ * entry synchronises or reads anything back.  Every random decision reads one fp32 uniform in [0,1) of `draws` [B, draw_stride]; per
+ * cloud, with M candidates, P slots and T = ROI_FG_AUG_TIMES:  key[M] | pick[P] | noise[P][T][9] | aug[P][3]
+ *   key:   the k foreground candidates with the smallest keys are taken, in key order (ties to the lower index): randperm(fg)[:k]
+ *   pick:  slot j takes candidate min(floor(pick[j] * n), n - 1) of its class, in index order
+ *   noise: per iteration [0] keep (kept when (double)u < 0.2), [1] range row min(floor(u * 5), 4), [2:5] position, [5:8] h w l, [8] angle
+ *   aug:   rotation, scale, flip of data_augmentation
+ * ------------------------------------------------------------------------------------- */
+int drc_rcnn_sample_max_candidates(void); /* 1024: LDS lists */
+int drc_rcnn_sample_max_slots(void);      /* 256: one lane per slot, one workgroup per cloud */
+/* sample_rois_for_rcnn, one workgroup per cloud: cand [B,M,7], gt [B,N,7] as [x,y,z,h,w,l,ry] -> rois [B,P,7] (after the noise loop),
+ * gt_of_rois [B,P,7], roi_iou [B,P], src_index [B,P] int32 (the candidate of each slot), n_iter [B,P] int32 (noise iterations run),
+ * counts [B,5] int32: fg, hard bg, easy bg candidates, fg slots, and 1 for a cloud with no fg and no bg candidate (its slots take
+ * candidates j mod M without noise; the reference raises there).  Slots: fg, hard bg, easy bg.  fg: iou >= fg_thresh
+ * (= min(REG_FG_THRESH, CLS_FG_THRESH), also the loop's stop); hard: bg_thresh_lo <= iou < bg_thresh; easy: iou < bg_thresh_lo;
+ * hard slots = (int)(bg slots * hard_bg_ratio) in double when both exist.  method 0: REG_AUG_METHOD 'multiple', 1: 'single'.
+ * 1 <= M <= drc_rcnn_sample_max_candidates(), 1 <= P <= drc_rcnn_sample_max_slots(), N >= 1, T >= 0, 0 <= fg_per_image <= P,
+ * draw_stride >= M + P + 9 P T + 3 P; otherwise -2 before any launch. */
+int drc_rcnn_sample_rois(int B, int M, int N, int P, int T, int fg_per_image, int method, float fg_thresh, float bg_thresh,
+                         float bg_thresh_lo, double hard_bg_ratio, const float* cand, const float* gt, const float* draws,
+                         int64_t draw_stride, float* rois, float* gt_of_rois, float* roi_iou, int32_t* src_index, int32_t* n_iter,
+                         int32_t* counts, void* stream);
+/* The training form of drc_rcnn_pool_canonical_fwd, one workgroup per (cloud, slot); inputs as there plus the sampler's rois, gt_of_rois,
+ * roi_iou [B,P(,7)] and counts [B,5].  The first S points inside the enlarged ROI are pooled; with aug != 0 the slot's rotation
+ * ((u - 1) * rot_range, rot_range = pi / AUG_ROT_RANGE), scale (1 + ((u - 0.5) / 0.5) * 0.05) and flip (sign(u - 0.5); 0 is no flip) from
+ * aug_draws [B, draw_stride] (the aug block: 3 per slot) are applied to the pooled coordinates, the ROI and its ground truth; then the
+ * canonical transform.  With aug == 0 no draw is read.  For r = b * P + slot:
+ *   xyz [R,S,3], pts [R,3+E,S], ofeat [R,C,S], empty_flag [R] int32 as drc_rcnn_pool_canonical_fwd (mask, depth, features un-augmented)
+ *   roi_boxes3d [R,7]  the augmented ROI;  gt_ct [R,7]  its ground truth: centre - ROI centre, ry - (roi_ry mod 2 pi), rotated by that
+ *   reg_valid_mask [R] int64 = iou > reg_fg & non-empty;  cls_label [R] int64 = iou > cls_fg, or -1 when empty or cls_bg < iou < cls_fg
+ *   a cloud flagged in counts[b][4]: cls_label -1, reg_valid_mask 0.
+ * Every element of every output is written.  1 <= S <= drc_box3d_max_pool_samples(). */
+int drc_rcnn_pool_target_fwd(int B, int N, int P, int C, int S, const float* rpn_xyz, const float* feat, const float* seg_mask,
+                             const float* pts_depth, int use_depth, const float* rois, const float* gt_of_rois, const float* roi_iou,
+                             const int32_t* counts, const float* aug_draws, int64_t draw_stride, int aug, float rot_range, float extra_width,
+                             float extra_width2, float reg_fg_thresh, float cls_fg_thresh, float cls_bg_thresh, float* xyz, float* pts,
+                             float* ofeat, int32_t* empty_flag, float* roi_boxes3d, float* gt_ct, int64_t* cls_label,
+                             int64_t* reg_valid_mask, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * PointRCNN training labels and losses (pts/train_targets.hip; net/point_rcnn.py:generate_rpn_training_labels, utils/loss_utils.py,
  * net/rpn_loss.py, net/rcnn_loss.py).  Labels are the reference's fp32 expressions in its order; loss values are evaluated and summed in
  * fp64 (per-block partials added in block order, no atomics: bit-identical run to run) and rounded once.  No entry synchronises.
