@@ -133,6 +133,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             wl[t] = *(const f16x8*)(wb + (t * 2 + 1) * 1024);
         }
     }
+    // Where they live: 216 weight registers + B fragments + epilogue do not fit the 256 arch VGPRs, so the allocator spilled
+    // fragments to AGPRs and copied each back (four v_accvgpr_read_b32) in front of its MFMA, every step.  An MFMA reads srcA from an AGPR
+    // as well: the empty asm below makes 41 fragments (164 registers) AGPR values, next to the 48 accumulator registers (+ 16 of the head's
+    // z_); pinning more pushes accumulators out into arch VGPRs and the VALU count up.  No instruction is emitted; the MFMAs stay builtins.
+    constexpr int PIN_WH = 14;
+#pragma unroll
+    for (int t = 0; t < 27; ++t) {
+        asm volatile("" : "+a"(wl[t]));
+        if (t < PIN_WH) asm volatile("" : "+a"(wh[t]));
+    }
     // ---- BN scale / shift of the couts this lane finishes: element e <-> cout ct*32 + 4g + 8*(own slot) + ...
     float sc[OWN], sh[OWN];
 #pragma unroll

@@ -107,6 +107,16 @@ __device__ __forceinline__ void body(const drc_s16conv_params& p, char* lds, int
             wh[t][kk] = *(const f16x8*)wb;
             wl[t][kk] = *(const f16x8*)(wb + 1024);
         }
+    // weights as AGPR values, read by the MFMAs directly (convs16.hip): as many fragments as fit next to the role's 2 * R.n
+    // accumulators, less four (with all of them the 1 x 28 form spills a VGPR); lo parts first, then hi
+    constexpr int PIN_ = (256 - 32 * R.n) / 4 - 4, PIN = PIN_ < 8 * NT ? PIN_ : 8 * NT;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            if (t * 4 + kk < PIN) asm volatile("" : "+a"(wl[t][kk]));
+            if (4 * NT + t * 4 + kk < PIN) asm volatile("" : "+a"(wh[t][kk]));
+        }
     // BN scale / shift of the 16 couts a lane holds (register e <-> cout (e&3) + 8(e>>2) + 4g), via LDS (read back per epilogue)
     if (wave == 0 && lane < 32) {
         const int gg = lane >> 4, e = lane & 15;

@@ -88,6 +88,17 @@ __device__ __forceinline__ void s16_cvrows_run(const drc_s16conv_params& p, char
                 wl[mi][kh][s] = *(const f16x8*)(wb + 1024);
             }
     }
+    // weights as AGPR values, read by the MFMAs directly (convs16.hip): 44 of the 60 fragments next to the five accumulators
+    constexpr int PIN_WH = 14;
+#pragma unroll
+    for (int mi = 0; mi < 5; ++mi)
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                asm volatile("" : "+a"(wl[mi][kh][s]));
+                if ((mi * 3 + kh) * 2 + s < PIN_WH) asm volatile("" : "+a"(wh[mi][kh][s]));
+            }
     // ---- assembly phase: this half wave's plane parity and 8-cout chunk (s, g): couts 16s + 4g + 8(e>>2) + (e&3), e = 0..7
     const int q8 = wave * 2 + hf, sg = q8 & 3, jpar = wave >> 1;
     const int grp0 = (sg >> 1) * 4 + (sg & 1), grp1 = grp0 + 2;       // 16-byte cout groups of a map column
