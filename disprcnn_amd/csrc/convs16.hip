@@ -73,6 +73,18 @@ constexpr int RING = 3;
 // the nine in-plane partial sums S[kh*3+kw][v] = sum_kd P[kd,kh,kw][z + kd - 1 plane of v] (48-byte slots [N][D][H][W][12] floats: j 0..4
 // at 0..4, j 5..8 at 8..11).  drc_head_gather_fwd then adds the nine shifted S values per output voxel (+ the previous head's cost).
 // HBM per voxel: 48 B written + 48 read instead of 128 written (blocked fp32) + ~175 read by the stand-alone cout-1 kernel.
+// ROWS layout (p.head_rows, W == 28 only: one x tile per row, so the three width taps of an OUTPUT column are held by neighbouring lanes of
+// the wave that produced them; run-time and wave-uniform, the 12-float layout above is untouched by it).  The width taps are summed here,
+// one-lane whole-wave DPP shifts (x - 1 at lane 0 and x + 1 at lane 63 read zero; the idle lanes 28..31 are zeroed first: lane 31 feeds lane
+// 32, lane 28 feeds lane 27), and the slot is float [N][D][H][W][4] = (T0, T1a, T1b, T2) per (source row, OUTPUT column):
+//     lane half 0 (j = 0..4):  T0  = (o0[x-1] + o1[x]) + o2[x+1]   (kh = 0)        T1a = o3[x-1] + o4[x]          (kh = 1: kw = 0, 1)
+//     lane half 1 (j = 5..8):  T1b = o0[x+1]                       (kh = 1: kw = 2) T2  = (o1[x-1] + o2[x]) + o3[x+1]   (kh = 2)
+// in exactly this order of additions in every lane, step kind (the drain's last plane included) and batch position.  Half 1's two values
+// move to half 0 (v_permlane32_swap, no arithmetic), whose lanes store the 16-byte slot.  There is NO branch on the layout inside a step (a
+// branch splits the tap group's block and its VALU work leaves the shadow of the MFMAs: measured +2.7 %): both layouts run the
+// same instructions -- the sums are always computed, the layout selects the data and the offsets of the same two stores (the second one
+// is dropped by its offset in the rows layout).  drc_head_gather_rows_fwd adds T0[y-1] + (T1a[y] + T1b[y]) + T2[y+1] of the same column:
+// 16 B written + 16 read per voxel.
 template <int KW, bool CV, int RT = 1, int WT = 28, bool RES = false, bool Y32 = false, bool HEAD = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void convs16_kernel(const drc_s16conv_params p) {
     static_assert(!HEAD || (KW == 2 && !CV && RT == 1 && !RES && !Y32), "the fused cout-1 head is a form of the 32 -> 32 full-resolution layer");
@@ -222,12 +234,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
     };
     // output context of a column: unit bases + this lane's voxel offsets (plane 0, padded coordinates + 1)
-    const long hs_planeB = (long)H * W * 48, hs_nB = (long)D * hs_planeB;          // HEAD: float [N][D][H][W][12]
+    const bool hrows = HEAD && p.head_rows;                                         // the rows layout: float [N][D][H][W][4]
+    const int hs_slotB = hrows ? 16 : 48;
+    const long hs_planeB = (long)H * W * hs_slotB, hs_nB = (long)D * hs_planeB;    // HEAD: float [N][D][H][W][12]
+    const bool hs_drop0 = hrows && g, hs_drop1 = hrows || g;                        // lanes whose first / second store is dropped by its offset
     struct Ctx { char* y16b; char* y32b; const char* resb; char* hsb; unsigned o16, o32, ohs; bool ok; };
     auto ctx_of = [&](const Col& c) __attribute__((always_inline)) {
         Ctx q;
         q.hsb = HEAD ? (char*)p.head + (long)c.n * hs_nB : (char*)p.w;
-        q.ohs = (unsigned)(((long)(c.y0 + r * RT + rl) * W + (c.x0 + xl)) * 48 + g * 32);
+        q.ohs = (unsigned)(((long)(c.y0 + r * RT + rl) * W + (c.x0 + xl)) * hs_slotB + (hrows ? 0 : g * 32));
         q.y16b = p.y16 ? (char*)p.y16 + (long)c.n * ynB : (char*)p.w;
         q.y32b = p.y32 ? (char*)p.y32 + (long)c.n * b_nB : (char*)p.w;
         q.resb = p.res ? (const char*)p.res + (long)c.n * ynB : (const char*)p.w;
@@ -270,6 +285,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // still open (SC: the next to complete; SB: the one after), five (kh, kw) per lane
     f32x16 pkeep = {};
     float SC[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, SB[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    // HEAD: what the first store of a step writes from five depth-summed values -- o[0..3] (12-float slots), or in the rows layout the
+    // width taps summed across lanes in the order of the header comment.  x - 1: wave_shr:1 (lane i reads lane i - 1), x + 1: wave_shl:1,
+    // bound_ctrl: a lane without a source reads zero; v_permlane32_swap(a, b)[1]: lanes 0..31 = a's lanes 32..63
+    auto head_pack = [&](const float* o) __attribute__((always_inline)) {
+        const bool live = n_ < WT;
+        int v_[5];
+#pragma unroll
+        for (int j = 0; j < 5; ++j) v_[j] = __builtin_bit_cast(int, live ? o[j] : 0.f);
+        auto left = [](int a) __attribute__((always_inline)) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, a, 0x138, 0xf, 0xf, true)); };
+        auto right = [](int a) __attribute__((always_inline)) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, a, 0x130, 0xf, 0xf, true)); };
+        auto own = [](int a) __attribute__((always_inline)) { return __builtin_bit_cast(float, a); };
+        const float a0 = (left(v_[0]) + own(v_[1])) + right(v_[2]);         // g = 0: T0
+        const float a1 = left(v_[3]) + own(v_[4]);                           // g = 0: T1a
+        const float b0 = right(v_[0]);                                       // g = 1: T1b
+        const float b1 = (left(v_[1]) + own(v_[2])) + right(v_[3]);         // g = 1: T2
+        const unsigned x0 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, b0), 0u, false, false)[1];
+        const unsigned x1 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, b1), 0u, false, false)[1];
+        u32x4 d;
+        d[0] = hrows ? __builtin_bit_cast(unsigned, a0) : __builtin_bit_cast(unsigned, o[0]);
+        d[1] = hrows ? __builtin_bit_cast(unsigned, a1) : __builtin_bit_cast(unsigned, o[1]);
+        d[2] = hrows ? x0 : __builtin_bit_cast(unsigned, o[2]);
+        d[3] = hrows ? x1 : __builtin_bit_cast(unsigned, o[3]);
+        return d;
+    };
     stage(s_cur, 0, 0);
     stage(s_cur, 1 < D ? 1 : D, 1);
     __builtin_amdgcn_s_waitcnt(S16_WAITCNT(NL, 15));      // plane 0 landed (step 0's own wait assumes a full previous step)
@@ -429,8 +468,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 const __amdgpu_buffer_rsrc_t hsr = __builtin_amdgcn_make_buffer_rsrc(scur ? cx_cur.hsb : cx_prev.hsb, 0, 0x7FFFFF00, 0x00020000);
                 const unsigned oh_ = scur ? cx_cur.ohs : cx_prev.ohs;
                 const unsigned po = ok_ ? (unsigned)((long)ps * hs_planeB) : 0x80000000u;
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, (f32x4){o_[0], o_[1], o_[2], o_[3]}), hsr, oh_ + po, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o_[4]), hsr, oh_ + 16 + (g ? 0x80000000u : po), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(head_pack(o_), hsr, oh_ + (hs_drop0 ? 0x80000000u : po), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o_[4]), hsr, oh_ + 16 + (hs_drop1 ? 0x80000000u : po), 0, 0);
             }
         };
         auto head_mfma = [&](int i) __attribute__((always_inline)) {
@@ -555,8 +594,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const bool ok_ = k == 0 && cx_cur.ok;
         const __amdgpu_buffer_rsrc_t hsr = __builtin_amdgcn_make_buffer_rsrc(cx_cur.hsb, 0, 0x7FFFFF00, 0x00020000);
         const unsigned po = ok_ ? (unsigned)((long)(D - 1) * hs_planeB) : 0x80000000u;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, (f32x4){SC[0], SC[1], SC[2], SC[3]}), hsr, cx_cur.ohs + po, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, SC[4]), hsr, cx_cur.ohs + 16 + (g ? 0x80000000u : po), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(head_pack(SC), hsr, cx_cur.ohs + (hs_drop0 ? 0x80000000u : po), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, SC[4]), hsr, cx_cur.ohs + 16 + (hs_drop1 ? 0x80000000u : po), 0, 0);
     }
     og.flush(p.ovf);
 }
@@ -617,8 +656,10 @@ extern "C" int drc_conv3d_k3_s16_fwd(const drc_s16conv_params* pp, void* stream)
     if (p.head) {                                                                   // fused cout-1 head: no tensor output, 32 -> 32 at full resolution
         if (!p.w1 || p.y16 || p.y32 || p.res || cv) return -1;
         if (p.cin != 32 || p.cout != 32 || p.W % 28 || p.D < 6 || p.D % 3) return -4;      // (the depth sums of the head close over real planes only)
+        if (p.head_rows && p.W != 28) return -4;                                    // the rows layout: one x tile per row
         if ((long)p.D * p.H * p.W * 48 >= 0x7FFFFF00L) return -5;
-    } else if (!p.y16 == !p.y32) return -1;                                         // exactly one output
+    } else if (p.head_rows) return -1;
+    else if (!p.y16 == !p.y32) return -1;                                         // exactly one output
     if (p.y32 && (p.res || p.cin != 32 || p.W <= 14)) return -4;                    // blocked fp32 output: the 32-channel layers on 1 x 28 tiles without residual
     if (cv && p.res) return -4;
     if (cv ? (!p.left || !p.right || p.cin != 64) : !p.x) return -1;

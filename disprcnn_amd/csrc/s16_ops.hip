@@ -272,3 +272,81 @@ extern "C" int drc_head_gather_fwd(const float* S, const float* res, float* cost
     hipLaunchKernelGGL(head_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, S, res, cost, total, H, W, scale);
     return (int)hipGetLastError();
 }
+
+// ---- the rows layout of the fused heads (convs16.hip, p.head_rows): the width taps are already summed, an output voxel adds three rows of
+// its own column -- and the three cumulative heads of a step are one launch.
+namespace {
+struct HeadRows {
+    const float* rows[3];
+    float scale[3];
+};
+// One thread per (unit, plane, column) walks the rows: every 16-byte slot is loaded exactly once (consecutive lanes = consecutive slots of a
+// row), four rows ahead; T0 of the row above and the slot of the row itself stay in registers.  No LDS, no halo.
+template <int NH>
+__global__ __launch_bounds__(256) void head_gather_rows_kernel(const HeadRows hr, const float* __restrict__ res, float* __restrict__ cost, long cols, int H, int W) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= cols) return;
+    const long plane = i / W;                                       // n * D + z
+    const long base = plane * H * W + (i - plane * W);              // voxel (y = 0, x) of the plane
+    const f32x4* r[NH];
+    f32x4 cur[NH];
+    float up[NH];
+#pragma unroll
+    for (int k = 0; k < NH; ++k) {
+        r[k] = (const f32x4*)hr.rows[k] + base;
+        cur[k] = r[k][0];
+        up[k] = 0.f;
+    }
+    for (int y0 = 0; y0 < H; y0 += 4) {
+        f32x4 nx[4][NH];
+        float rs[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int yn = y0 + j + 1 < H ? y0 + j + 1 : H - 1, yr = y0 + j < H ? y0 + j : H - 1;       // (clamped: a row outside the plane is never read)
+#pragma unroll
+            for (int k = 0; k < NH; ++k) nx[j][k] = r[k][(long)yn * W];
+            rs[j] = res ? res[base + (long)yr * W] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int y = y0 + j;
+            if (y < H) {
+                float c = rs[j];
+#pragma unroll
+                for (int k = 0; k < NH; ++k) {
+                    float s = up[k] + (cur[k][1] + cur[k][2]);      // (y == 0: up = 0, the skipped row)
+                    if (y + 1 < H) s += nx[j][k][3];
+                    c = hr.scale[k] * s + c;
+                }
+                cost[base + (long)y * W] = c;
+            }
+#pragma unroll
+            for (int k = 0; k < NH; ++k) {
+                up[k] = cur[k][0];
+                cur[k] = nx[j][k];
+            }
+        }
+    }
+}
+}  // namespace
+
+extern "C" int drc_head_gather_rows_fwd(const float* rows0, const float* rows1, const float* rows2, float scale0, float scale1, float scale2, int nheads,
+                                        const float* res, float* cost, int N, int D, int H, int W, void* stream) {
+    if (nheads < 1 || nheads > 3) return -2;
+    const HeadRows hr = {{rows0, rows1, rows2}, {scale0, scale1, scale2}};
+    for (int k = 0; k < nheads; ++k)
+        if (!hr.rows[k] || ((uintptr_t)hr.rows[k] & 15)) return -1;
+    if (!cost) return -1;
+    if (N < 0 || D <= 0 || H <= 0 || W <= 0) return -2;
+    if (N == 0) return 0;
+    const long cols = (long)N * D * W;
+    const long blocks = (cols + 255) / 256;
+    if (blocks > 0x7fffffffL) return -3;
+    const dim3 g((unsigned)blocks), b(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (nheads == 1) hipLaunchKernelGGL(head_gather_rows_kernel<1>, g, b, 0, s, hr, res, cost, cols, H, W);
+    else if (nheads == 2) hipLaunchKernelGGL(head_gather_rows_kernel<2>, g, b, 0, s, hr, res, cost, cols, H, W);
+    else hipLaunchKernelGGL(head_gather_rows_kernel<3>, g, b, 0, s, hr, res, cost, cols, H, W);
+    return (int)hipGetLastError();
+}

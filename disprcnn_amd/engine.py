@@ -997,6 +997,23 @@ def head_gather(S, scale, res, out):
     _lib.check(st, "drc_head_gather_fwd")
 
 
+def head_gather_rows(rows, scales, res, out):
+    """The second half of 1 to 3 fused heads in the rows layout (ConvPlanS16.run(head=..., head_rows=True)), cumulative: out dense [N,D,H,W] =
+    (res or 0), then per head scale_k * (T0_k[y-1] + (T1a_k[y] + T1b_k[y]) + T2_k[y+1]) added in order; rows: fp32 buffers [N][D][H][W][4]."""
+    N, D, H, W = out.shape
+    if not 1 <= len(rows) <= 3 or len(scales) != len(rows):
+        raise ValueError("head_gather_rows: 1 to 3 heads, one scale each")
+    for r in rows:
+        if r.dtype != torch.float32 or r.numel() < N * D * H * W * 4 or not r.is_contiguous():
+            raise ValueError("head_gather_rows: rows = contiguous fp32 buffers of N*D*H*W*4")
+    if out.dtype != torch.float32 or not out.is_contiguous() or (res is not None and (res.dtype != torch.float32 or res.shape != out.shape or not res.is_contiguous())):
+        raise ValueError("head_gather_rows: out / res = contiguous fp32 [N,D,H,W]")
+    ptrs = [_ptr(r) for r in rows] + [None] * (3 - len(rows))
+    sc = [C.c_float(float(s)) for s in scales] + [C.c_float(0.0)] * (3 - len(rows))
+    st = _lib.lib().drc_head_gather_rows_fwd(ptrs[0], ptrs[1], ptrs[2], sc[0], sc[1], sc[2], len(rows), _ptr(res), _ptr(out), N, D, H, W, _stream_ptr(out.device))
+    _lib.check(st, "drc_head_gather_rows_fwd")
+
+
 def upsample_softargmin(cost, disp, maxdisp, mindisp):
     N, Dp, Hp, Wp = cost.shape
     _, H, W = disp.shape
@@ -1370,6 +1387,7 @@ def cost_volume16_blocked(left, right, out, lo4, hi4, in_blocked_pad=-1):
 HEAD_FUSED = {"enabled": True}       # eval, split-f16 regressor: classif[0] + the 32 -> 1 layer as one fused launch + a gather (convs16.hip HEAD form) instead of a blocked fp32 tensor + cout1_mfma.hip
 LASTCONV_S16 = {"enabled": True}     # eval, split-f16 2D schedule: lastconv[0] (320 -> 128) as three chained split-f16 launches over the concat's parts (runtime._ws2d_s16)
 S16 = {"enabled": True}       # eval: the stride-1 3x3x3 layers at full resolution on the f16 matrix cores in split arithmetic (convs16.hip)
+HEAD_ROWS = {"enabled": True}        # eval, fused heads on 28-column maps: the head launches sum the width taps (rows layout, 16 B per voxel) and ONE gather adds the three heads into cost3; False: the 12-float slots + a gather per head (A/B switch, read at every forward)
 CV_WIDE = {"enabled": True}   # eval, large batches: the cost-volume layer with two rows per work item (convs16w.hip); False: convs16.hip's one-row form (A/B switch, read at every run())
 
 
@@ -1628,15 +1646,18 @@ class ConvPlanS16:
     def _wide(self):
         return self.kind == "s1" and self._wide_ok and bool(CV_WIDE["enabled"])
 
-    def run(self, x16, w16, scale, shift, y16=None, y32=None, res=None, left=None, right=None, lo4=0, head=None):
+    def run(self, x16, w16, scale, shift, y16=None, y32=None, res=None, left=None, right=None, lo4=0, head=None, head_rows=False):
         """head = (packed 32 -> 1 weights of s16.pack_head_weight_s16, S buffer fp32 of >= N*D*H*W*12 floats): the layer is classif[0] of a
-        head, its output is not stored, the partial sums of the cout-1 layer behind it are (head_gather finishes it)."""
+        head, its output is not stored, the partial sums of the cout-1 layer behind it are (head_gather finishes it).  head_rows (W == 28): the
+        rows layout, S of >= N*D*H*W*4 floats, finished by head_gather_rows."""
         from ._lib import DrcS16ConvParams
         if head is not None:
             if self.kind != "s1" or self.cv or (self.cin, self.cout) != (32, 32) or self.W % 28 or self.D < 6 or self.D % 3 or y16 is not None or y32 is not None or res is not None:
                 raise ValueError("ConvPlanS16.run: the fused head is the 32 -> 32 full-resolution layer without another output")
-            if head[1].dtype != torch.float32 or head[1].numel() < self.N * self.D * self.H * self.W * 12 or head[0].dtype != torch.float16 or head[0].numel() != 2048:
-                raise ValueError("ConvPlanS16.run: head = (halfs [2][2][64][8], fp32 buffer of N*D*H*W*12)")
+            if head[1].dtype != torch.float32 or head[1].numel() < self.N * self.D * self.H * self.W * (4 if head_rows else 12) or head[0].dtype != torch.float16 or head[0].numel() != 2048:
+                raise ValueError("ConvPlanS16.run: head = (halfs [2][2][64][8], fp32 buffer of N*D*H*W*12; rows layout: *4)")
+        elif head_rows:
+            raise ValueError("ConvPlanS16.run: head_rows is a layout of the fused head")
         if x16 is not None and (x16.N < self.N or (x16.C, x16.D, x16.H, x16.W, x16.pd) != (self.cin, self.D, self.H, self.W, self.pd)):
             raise ValueError("ConvPlanS16.run: input geometry differs from the plan")
         for t_ in (y16, res):
@@ -1659,7 +1680,7 @@ class ConvPlanS16:
                              _ptr(y32.storage) if y32 is not None else None, _ptr(left.storage) if self.cv else None,
                              _ptr(right.storage) if self.cv else None, self.N, self.D, self.H, self.W, self.cin, self.cout, int(self.relu), int(lo4),
                              0x800 if (self.cv and self.kind == "s1" and not CV_WIDE["enabled"]) else int(self.dil),   # (the library's experiment bit of the 3D layers' unused `dil` field: keep the one-row kernel)
-                             _ptr(head[1]) if head is not None else None, _ptr(head[0]) if head is not None else None, _ovf_ptr())
+                             _ptr(head[1]) if head is not None else None, _ptr(head[0]) if head is not None else None, _ovf_ptr(), int(bool(head_rows)))
         dev = self.device
         if TIMING is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

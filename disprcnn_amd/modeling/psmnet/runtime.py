@@ -568,6 +568,14 @@ class PSMNetRuntime:
             run(f"hg{k}.conv6", hg + ".conv6", f"hg{k}.post", y16=f"out{k}", res="cost0")       # out_k = conv6 + cost0
         prev = None
         h16 = self._head_weights_s16() if ws["fused_heads"] else None
+        if h16 is not None and E.HEAD_ROWS["enabled"] and t["costk3"].shape[-1] == 28:
+            # one x tile per row: the head launches sum the width taps themselves (rows layout, 16 B per voxel: the S buffer holds all three
+            # heads) and ONE gather adds the three heads into cost3 -- cost1 / cost2 are the training path's and are not produced here
+            rows = t["hs"].view(3, -1)
+            for k in (1, 2, 3):
+                run(f"classif{k}.0", f"classif{k}.0", f"out{k}", head=(h16[k][0], rows[k - 1]), head_rows=True)
+            E.head_gather_rows([rows[0], rows[1], rows[2]], [h16[k][1] for k in (1, 2, 3)], None, t["costk3"])
+            return None, None, t["costk3"]
         for k in (1, 2, 3):
             if h16 is not None:
                 run(f"classif{k}.0", f"classif{k}.0", f"out{k}", head=(h16[k][0], t["hs"]))
@@ -808,7 +816,7 @@ class PSMNetRuntime:
         m = self.model
         return (m.maxdisp, m.mindisp, getattr(m, "regressor_math", "auto"), getattr(m, "regressor_storage", "f32"),
                 getattr(m, "feature_storage", "f32"), getattr(m, "feature_math", "auto"),
-                E.S16["enabled"], E.HEAD_FUSED["enabled"], E.LASTCONV_S16["enabled"], E.TRUNK_S16["enabled"], E.CV_WIDE["enabled"], E.s16_allowed(),
+                E.S16["enabled"], E.HEAD_FUSED["enabled"], E.LASTCONV_S16["enabled"], E.TRUNK_S16["enabled"], E.CV_WIDE["enabled"], E.HEAD_ROWS["enabled"], E.s16_allowed(),
                 id(E.guard_in_scope()))
 
     def forward_features(self, fl, fr, out_hw, training=False):

@@ -373,6 +373,10 @@ typedef struct drc_s16conv_params {
     uint32_t* ovf;       /* optional device word (round 6): OR-ed with 1 when a value this launch stores (or, with head, multiplies) left the
                             split-f16 range before the clamp -- |v| > 65504, Inf or NaN.  The reference is fp32 (config/defaults.py:22) and has no
                             such limit: the caller reads the word once per forward and re-runs on the fp32 kernels or raises.  NULL: no report. */
+    int32_t head_rows;   /* with head, W == 28 (else -4): the ROWS layout of the partial sums, float [N][D][H][W][4] = (T0, T1a, T1b, T2) per source
+                            row and OUTPUT column -- the width taps summed in the kernel: T0 = (S0[x-1] + S1[x]) + S2[x+1], T1a = S3[x-1] + S4[x],
+                            T1b = S5[x+1], T2 = (S6[x-1] + S7[x]) + S8[x+1] (a column outside the map adds zero).  drc_head_gather_rows_fwd
+                            finishes the layer.  0: the 12-float layout above. */
 } drc_s16conv_params;
 int drc_conv3d_k3_s16_supported(int cin, int cout, int D, int H, int W);
 int drc_conv3d_k3_s16_fwd(const drc_s16conv_params* p, void* stream);
@@ -388,6 +392,12 @@ int drc_conv3d_k3_s16_wide_fwd(const drc_s16conv_params* p, void* stream);
  * (sources outside the volume contribute zero: the convolution's zero padding); cost, res: dense float [N][D][H][W] (res = the previous
  * head's cost, stackhourglass.py:142-144, or NULL); scale = 2^-wexp of the packed 32 -> 1 weights. */
 int drc_head_gather_fwd(const float* S, const float* res, float* cost, int N, int D, int H, int W, float scale, void* stream);
+/* The second half of 1 to 3 fused heads in the rows layout (p->head_rows above), the cumulative head add of stackhourglass.py:142-144 in ONE
+ * launch:  c = res ? res[n][z][y][x] : 0;  for k = 0 .. nheads-1:  c = scale_k * ((T0_k[y-1] + (T1a_k[y] + T1b_k[y])) + T2_k[y+1]) + c  (a product and a sum
+ * per head, as drc_head_gather_fwd; same column x; a row outside [0, H) is skipped, never read);  cost[n][z][y][x] = c.  rows_k: float [N][D][H][W][4], 16-byte
+ * aligned; rows / scales of k >= nheads are ignored. */
+int drc_head_gather_rows_fwd(const float* rows0, const float* rows1, const float* rows2, float scale0, float scale1, float scale2, int nheads,
+                             const float* res, float* cost, int N, int D, int H, int W, void* stream);
 /* The hourglass' other 3x3x3 layers in the same arithmetic and layout (x, y16, res: RS16; no blocked fp32 output, no cost-volume form):
  *   drc_conv3d_k3s2_s16_fwd   -- Conv3d k3 s2 p1 + BN + ReLU (convs16d.hip; reference hourglass conv1 / conv3, stackhourglass.py:9-12,17-19).
  *                                D, H, W = the INPUT dims (even); y16 has (D/2, H/2, W/2); no residual.
