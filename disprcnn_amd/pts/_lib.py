@@ -67,6 +67,11 @@ _SIGS = {
     "drc_kitti_eval_pass1": (_I, [_I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _D, _D, _D, _P, _P, _P]),
     "drc_kitti_eval_pass2": (_I, [_I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _D, _D, _D, _I, _P, _P, _P, _P, _P]),
     "drc_kitti_eval_reduce": (_I, [_I, _P, _P, _P, _P, _P]),
+    "drc_solver_chunk": (_I, []),
+    "drc_solver_grad_norm": (_I, [_L, _L, _P, _P, _P, _P]),
+    "drc_solver_prepare": (_I, [_L, _P, _I, _F, _I, _I, _P, _P, _P, _P, _P]),
+    "drc_solver_sgd_step": (_I, [_L, _L, _I, _P, _P, _P, _P, _P, _I, _P]),
+    "drc_solver_adam_step": (_I, [_L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -325,6 +325,35 @@ int drc_kitti_eval_pass2(int F, int NG, int ND, int64_t NP, int max_gt, int max_
  * bit-identical run to run. */
 int drc_kitti_eval_reduce(int F, const int16_t* counts, const double* sim, int64_t* out_counts, double* out_sim, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The solver (solver.hip): gradient norm, clipping and the SGD / Adam update of ALL parameter tensors in three launches.
+ *
+ * The host builds the work table once (disprcnn_amd/solver/fused.py):
+ *   tensors int64 [T,5]: parameter pointer, gradient pointer, offset into the flat state buffers (floats, a multiple of 4), numel, group
+ *   chunks  int64 [C,2]: tensor, start (a multiple of drc_solver_chunk()); one workgroup per chunk, none for an empty tensor
+ *   hyper   fp32  [G,8]: lr, weight_decay, momentum | beta1, beta2, eps, 1 - beta1, 1 - beta2, 0
+ *   derived fp32  [G,2]: Adam's lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t), written by drc_solver_prepare
+ *   scalars fp32  [4]  : total_norm, clip_coef, the step count as a float, 0;   step int64 [1]: the step count
+ * Parameters and gradients need 4-byte alignment only.  Every sum has a fixed order: bit-identical run to run.
+ * ------------------------------------------------------------------------------------- */
+int drc_solver_chunk(void);
+/* partials [C] fp64 <- the sum of g^2 over each chunk */
+int drc_solver_grad_norm(int64_t n_chunks, int64_t n_tensors, const int64_t* tensors, const int64_t* chunks, double* partials,
+                         void* stream);
+/* flags: 1 = add the partials in chunk order, write total_norm and clip_coef = min(1, max_norm / (total_norm + 1e-6));
+ *        2 = leave clip_coef as an earlier call wrote it (without 1 and 2 it becomes 1);
+ *        4 = advance the step count and, for Adam, write `derived` for the new count. */
+int drc_solver_prepare(int64_t n_chunks, const double* partials, int flags, float max_norm, int n_groups, int adam, const float* hyper,
+                       float* derived, float* scalars, int64_t* step, void* stream);
+/* torch.optim.SGD (dampening 0, no Nesterov): d = g + wd * p; buf = momentum * buf + d; p -= lr * buf.  momentum_buf may be null
+ * (momentum 0).  clip != 0: g is scaled by clip_coef first and written back, as clip_grad_norm_ leaves it. */
+int drc_solver_sgd_step(int64_t n_chunks, int64_t n_tensors, int n_groups, const int64_t* tensors, const int64_t* chunks,
+                        const float* hyper, const float* scalars, float* momentum_buf, int clip, void* stream);
+/* torch.optim.Adam (no amsgrad, L2 weight decay on the gradient), bias correction from `derived` */
+int drc_solver_adam_step(int64_t n_chunks, int64_t n_tensors, int n_groups, const int64_t* tensors, const int64_t* chunks,
+                         const float* hyper, const float* derived, const float* scalars, float* exp_avg, float* exp_avg_sq, int clip,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
