@@ -17,7 +17,7 @@
 // One arithmetic, one summation order per output value, whatever kernel, workgroup or wave produces it: both kernels of the family that have a
 // cost-volume form (convs16_kernel<4,true,...>: one row per work item; convs16w_kernel<4,true>: two) run s16_cvrows_run below.
 //   map value:    kh 0..2 outer, K slice (16 channels) 0..1 inner, each product hi*hi, then lo(act)*hi(w), then hi(act)*lo(w), fp32 accumulate
-//   output value: kd 0..2 outer, kw 0..2 inner, acc += (A + B); masked terms add +0.
+//   output value: kd 0..2 outer, kw 0..2 inner, acc += (A + B), the sum rounded once; masked terms add +0.
 //
 // Work item: (unit, ROWS consecutive rows, x tile of 28 columns, group of <= 32 planes).  Per row, four waves:
 //   stage    rows y-1..y+1 of L (columns x0-1 .. x0+30) and of R (the columns the tile's planes reach: <= 63, one or two 32-column tiles)
@@ -25,9 +25,14 @@
 //   maps     waves 0/1: A maps 0..4 / 4..8, waves 2/3: B maps 0..4 / 4..8 (90 MFMAs per wave and 32-column tile; weights register-resident:
 //            5 maps x 3 kh x 2 slices x (hi, lo) = 240 VGPRs), published to LDS as fp32 [map][column][32 couts], 16-byte groups XOR-swizzled
 //            by the column so that both the MFMA lanes' writes and the assembling lanes' reads are conflict-free;
-//   assemble a half wave owns (plane parity, one of the four 8-cout chunks) x 28 columns: 36 ds_read_b128 per plane, then the family's
-//            epilogue (BN scale / shift, ReLU, clamp with the s16_ovf.h guard, hi / lo split, two 16-byte RS16 stores).  The right-side shift
-//            is an address offset; a masked term reads a zero column.  The zero halo is never written.
+//   assemble a half wave owns (plane parity, one of the four 8-cout chunks) x 28 columns.  With one wave per SIMD the loop is bound by the
+//            number of instructions it issues, of any kind, so it is written for few of them: the nine left terms x two
+//            cout groups are loaded once per row into registers (they do not depend on the plane, only their mask does); per plane 18
+//            ds_read_b128 of the right terms, whose five distinct columns move by two from a plane to the wave's next (three offsets and
+//            masks are carried over, two computed); a term is fma(A, ok ? 1 : 0, B) -- B of a masked term is read from a zero column, so
+//            the masked term is +0 and an unmasked one the rounded A + B, bit for bit what reading both from LDS gave (map values are
+//            finite); then the family's epilogue (BN scale / shift, ReLU, clamp with the s16_ovf.h guard, hi / lo split, two 16-byte RS16
+//            stores).  The right-side shift is an address offset.  The zero halo is never written.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,6 +55,7 @@ constexpr int MAP_TILE = 9 * MAP_B;
 constexpr int STG0 = 0, MAPS0 = 3 * STG_TILE, ZCOL0 = MAPS0 + 3 * MAP_TILE;
 constexpr int LDS_BYTES = ZCOL0 + 128;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+static_assert(ZCOL0 % 64 == 0, "a column's second cout group is its first ^ 32, in the zero column too");
 
 #define S16CV_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define S16CV_WAITCNT(vm, lgkm) (((vm) & 15) | (7 << 4) | ((lgkm) << 8) | (((vm) >> 4) << 14))
@@ -101,7 +107,7 @@ __device__ __forceinline__ void s16_cvrows_run(const drc_s16conv_params& p, char
             }
     // ---- assembly phase: this half wave's plane parity and 8-cout chunk (s, g): couts 16s + 4g + 8(e>>2) + (e&3), e = 0..7
     const int q8 = wave * 2 + hf, sg = q8 & 3, jpar = wave >> 1;
-    const int grp0 = (sg >> 1) * 4 + (sg & 1), grp1 = grp0 + 2;       // 16-byte cout groups of a map column
+    const int grp0 = (sg >> 1) * 4 + (sg & 1);        // 16-byte cout groups of a map column: grp0 and grp0 + 2 = grp0 ^ 2, 32 bytes apart by XOR
     float sc[8], sh[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -244,28 +250,80 @@ __device__ __forceinline__ void s16_cvrows_run(const drc_s16conv_params& p, char
         const unsigned long long og_keep = S16Ovf::lanes(lane_ok);
         const __amdgpu_buffer_rsrc_t y16r = __builtin_amdgcn_make_buffer_rsrc((char*)p.y16 + (long)t.n * ynB, 0, 0x7FFFFF00, 0x00020000);
         const unsigned o16 = (unsigned)((long)ct * xcbB + planeB + (long)(t.y + 1) * rowB + (long)sg * (Wp * 16) + (long)(x + 1) * 16);
-        const int xa0 = t.x0 - 1;
-#pragma unroll 1
-        for (int j = t.j0 + jpar; j < t.j1; j += 2) {
-            const int u = x - (lo4 + j);
-            f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+        // byte offset of cout group grp0 of column c (0..31) inside a map: the 16-byte groups are XOR-swizzled by the column
+        auto col_off = [&](unsigned c) __attribute__((always_inline)) { return c * 128u + (((unsigned)grp0 ^ (c & 7u)) << 4); };
+        // the left terms A[kd][kw](y, x + kw - 1): once per row.  A term whose column is outside the map holds the zero column
+        bool okA[3];
+        f32x4 ar0[9], ar1[9];
 #pragma unroll
-            for (int kd = 0; kd < 3; ++kd) {
-                const bool kd_ok = lane_ok && j + kd - 1 >= 0 && j + kd - 1 < D;
+        for (int kw = 0; kw < 3; ++kw) {
+            const int cA = x + kw - 1;
+            okA[kw] = lane_ok && cA >= 0 && cA < W;
+        }
+#pragma unroll
+        for (int m = 0; m < 9; ++m) {
+            const int kw = m % 3;
+            const unsigned oa = okA[kw] ? (unsigned)MAPS0 + col_off((unsigned)(xl + kw) & 31u) : (unsigned)(ZCOL0 - m * MAP_B);
+            ar0[m] = *(lds_f4*)(ldsl + oa + m * MAP_B);
+            ar1[m] = *(lds_f4*)(ldsl + (oa ^ 32u) + m * MAP_B);
+        }
+        // the right column u + (kw - kd), u = x - s_j, takes five values u - 2 .. u + 2: offset (tile, column, swizzled group) and mask of each
+        auto off_of = [&](int cB) __attribute__((always_inline)) {
+            const int ib = cB - rc.vlo;
+            return (unsigned)(MAPS0 + MAP_TILE) + (unsigned)(ib >> 5) * (unsigned)MAP_TILE + col_off((unsigned)ib & 31u);
+        };
+        unsigned offB[5];
+        bool okB[5];
+        const int jb = t.j0 + jpar;
+#pragma unroll
+        for (int d = 0; d < 5; ++d) {
+            const int cB = x - (lo4 + jb) + d - 2;
+            offB[d] = off_of(cB);
+            okB[d] = (unsigned)cB < (unsigned)W;
+        }
+#pragma unroll 1
+        for (int j = jb; j < t.j1; j += 2) {
+            f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+            f32x4 B0[9], B1[9];
+            float msk[9];
+            auto read = [&](int kd) __attribute__((always_inline)) {
+                const bool kd_ok = j + kd - 1 >= 0 && j + kd - 1 < D;
 #pragma unroll
                 for (int kw = 0; kw < 3; ++kw) {
-                    const int cA = x + kw - 1, cB = u + kw - kd;
-                    const bool ok = kd_ok && cA >= 0 && cA < W && cB >= 0 && cB < W;
-                    const int ia = cA - xa0, ib = cB - rc.vlo;
-                    const int m = kd * 3 + kw;
-                    const unsigned colA = ok ? (unsigned)(MAPS0 + m * MAP_B + ia * 128) : (unsigned)ZCOL0;
-                    const unsigned colB = ok ? (unsigned)(MAPS0 + MAP_TILE + (ib >> 5) * MAP_TILE + m * MAP_B + (ib & 31) * 128) : (unsigned)ZCOL0;
-                    const unsigned swA = (unsigned)(ia & 7), swB = (unsigned)(ib & 7);
-                    const f32x4 A0 = *(lds_f4*)(ldsl + colA + ((grp0 ^ swA) * 16)), A1 = *(lds_f4*)(ldsl + colA + ((grp1 ^ swA) * 16));
-                    const f32x4 B0 = *(lds_f4*)(ldsl + colB + ((grp0 ^ swB) * 16)), B1 = *(lds_f4*)(ldsl + colB + ((grp1 ^ swB) * 16));
-                    a0 += A0 + B0;
-                    a1 += A1 + B1;
+                    const int m = kd * 3 + kw, d = kw - kd + 2;
+                    const bool ok = okA[kw] && kd_ok && okB[d];
+                    const unsigned ob = ok ? offB[d] : (unsigned)(ZCOL0 - m * MAP_B);
+                    B0[m] = *(lds_f4*)(ldsl + ob + m * MAP_B);
+                    B1[m] = *(lds_f4*)(ldsl + (ob ^ 32u) + m * MAP_B);
+                    msk[m] = ok ? 1.f : 0.f;
                 }
+            };
+            auto add = [&](int kd) __attribute__((always_inline)) {          // kw inner: acc += (A + B), or += +0
+#pragma unroll
+                for (int kw = 0; kw < 3; ++kw) {
+                    const int m = kd * 3 + kw;
+                    const f32x4 k = {msk[m], msk[m], msk[m], msk[m]};
+                    a0 += __builtin_elementwise_fma(ar0[m], k, B0[m]);
+                    a1 += __builtin_elementwise_fma(ar1[m], k, B1[m]);
+                }
+            };
+            // one wait per kd instead of one per term
+#pragma unroll
+            for (int kd = 0; kd < 3; ++kd) {
+                read(kd);
+                __builtin_amdgcn_s_waitcnt(S16CV_WAITCNT(63, 0));
+                __builtin_amdgcn_sched_barrier(0);
+                add(kd);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            // the wave's next plane j + 2: the right columns move by two
+            offB[4] = offB[2]; offB[3] = offB[1]; offB[2] = offB[0];
+            okB[4] = okB[2]; okB[3] = okB[1]; okB[2] = okB[0];
+#pragma unroll
+            for (int d = 0; d < 2; ++d) {
+                const int cB = x - (lo4 + j + 2) + d - 2;
+                offB[d] = off_of(cB);
+                okB[d] = (unsigned)cB < (unsigned)W;
             }
             f16x8 hi, lo;
 #pragma unroll
