@@ -8,14 +8,19 @@ kernels read weights K-major, so a raw pair is transposed on the device at every
 no autograd; there is no torch fallback.  `sa_mlp_max_unfused` is the same arithmetic done the long way
 (grouping_operation -> conv2d -> max) for tools/bench_rpn.py and the tests to compare against; the modules never call it.
 
-Training forms (autograd, on the backward kernels of pts/pn2_mlp_bwd.hip; layers without BatchNorm only):
+Training forms (autograd, on the backward kernels of pts/pn2_mlp_bwd.hip and the BatchNorm kernels of pts/pn2_bn.hip):
 
     pointwise_mlp_train(in0, in1, weight, bias, relu)        one layer; gradients for in0, in1, weight (its own shape) and bias
+    bn_act_train(y, bn_weight, bn_bias, running_mean, running_var, momentum, eps, relu)
+                                                             act(BatchNorm(y)) on the statistics of the batch, running statistics updated
+    pointwise_bn_train(in0, in1, weight, bn, relu)           conv without bias -> bn_act_train with the nn.BatchNorm module `bn`
     group_max(x)                                             (B,C,M,ns) -> (B,C,M), the max over ns; ties go to the lowest sample
     sa_mlp_max_train(xyz, new_xyz, feats, idx, layers)       group -> subtract the centre -> layers -> group_max, all in HBM
 
-The weight gradient is summed in fp32 within a chunk of `WGRAD_CHUNK` columns and in fp64 across chunks, in chunk order: bit-identical
-run to run, and its bits depend on WGRAD_CHUNK.
+A training layer is (weight, bias), or (weight, None, bn) with an nn.BatchNorm1d / 2d module after a conv without bias.  The weight
+gradient is summed in fp32 within a chunk of `WGRAD_CHUNK` columns and in fp64 across chunks, in chunk order; the BatchNorm sums are fp64
+throughout, per chunk of `BN_CHUNK` columns and then across chunks in chunk order: bit-identical run to run, and the bits depend on the
+chunk lengths.
 """
 import torch
 import torch.nn.functional as F
@@ -24,6 +29,7 @@ from .. import engine as E
 from ..pts import _lib
 
 WGRAD_CHUNK = 2048          # pts/pn2_mlp_bwd.hip:kWgradChunk (checked against the library when it is first used)
+BN_CHUNK = 4096             # pts/pn2_bn.hip:kBnChunk (likewise)
 
 
 class Packed:
@@ -252,6 +258,142 @@ def pointwise_mlp_train(in0, in1, weight, bias, relu):
     return _PointwiseMlpTrain.apply(in0, in1, weight, bias, bool(relu))
 
 
+# ---- BatchNorm on the statistics of the batch
+def _bn_workspace(B, C, N, dev):
+    got = _lib.lib().drc_pn2_bn_chunk()
+    if got != BN_CHUNK:
+        raise RuntimeError(f"pn2_mlp: the library was built with a BatchNorm chunk of {got}, this module expects {BN_CHUNK}")
+    n_ws = _lib.lib().drc_pn2_bn_workspace_doubles(B, C, N)
+    if n_ws < 0:
+        raise RuntimeError(f"drc_pn2_bn_workspace_doubles failed: status {n_ws}")
+    return torch.empty(n_ws, dtype=torch.float64, device=dev)
+
+
+class _BnActTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, bn_weight, bn_bias, running_mean, running_var, momentum, eps, relu):
+        B, C, N = y.shape
+        dev = y.device
+        y = y.contiguous()
+        stats = torch.empty((2, C), dtype=torch.float32, device=dev)
+        z = torch.empty_like(y)
+        st = _lib.lib().drc_pn2_bn_stats(B, C, N, E._ptr(y), E._ptr(_bn_workspace(B, C, N, dev)), eps, momentum, E._ptr(stats),
+                                         E._ptr(running_mean), E._ptr(running_var), E._stream_ptr(dev))
+        _lib.check(st, "drc_pn2_bn_stats")
+        st = _lib.lib().drc_pn2_bn_apply_fwd(B, C, N, 1 if relu else 0, E._ptr(y), E._ptr(stats), E._ptr(bn_weight), E._ptr(bn_bias),
+                                             E._ptr(z), E._stream_ptr(dev))
+        _lib.check(st, "drc_pn2_bn_apply_fwd")
+        ctx.relu = bool(relu)
+        ctx.save_for_backward(y, z, stats, bn_weight)
+        ctx.mark_non_differentiable(stats)
+        return z, stats
+
+    @staticmethod
+    def backward(ctx, gz, _gstats):
+        y, z, stats, bn_weight = ctx.saved_tensors
+        B, C, N = y.shape
+        dev = y.device
+        E.require_gpu(gz, "bn_act_train (backward)")
+        gz = gz.contiguous()
+        gy = torch.empty_like(y)
+        gg = torch.empty(C, dtype=torch.float32, device=dev)
+        gb = torch.empty(C, dtype=torch.float32, device=dev)
+        st = _lib.lib().drc_pn2_bn_bwd(B, C, N, 1 if ctx.relu else 0, E._ptr(gz), E._ptr(z), E._ptr(y), E._ptr(stats), E._ptr(bn_weight),
+                                       E._ptr(_bn_workspace(B, C, N, dev)), E._ptr(gy), E._ptr(gg), E._ptr(gb), E._stream_ptr(dev))
+        _lib.check(st, "drc_pn2_bn_bwd")
+        return gy, gg, gb, None, None, None, None, None
+
+
+def bn_act_train(y, bn_weight, bn_bias, running_mean, running_var, momentum, eps, relu, return_stats=False):
+    """torch.nn.BatchNorm1d / 2d in training mode, then ReLU when `relu`, with autograd: y (B,C,N), bn_weight / bn_bias [C] ->
+    z = act(bn_weight * (y - mean) / sqrt(var + eps) + bn_bias) with the mean and the biased variance of each channel over its B * N
+    values.  running_mean / running_var [C] (both None, or both given) are updated in place, r <- (1 - momentum) r + momentum * (mean |
+    var * n / (n - 1)); through raw pointers, so their `_version` does not move.  Gradients go to y, bn_weight and bn_bias.
+    return_stats: -> (z, stats [2,C]: mean, 1 / sqrt(var + eps))."""
+    what = "bn_act_train"
+    E.require_gpu(y, what)
+    if y.dim() != 3:
+        raise RuntimeError(f"{what}: y must be [B,C,N], got {tuple(y.shape)}")
+    B, C, N = y.shape
+    for name, t in (("bn_weight", bn_weight), ("bn_bias", bn_bias), ("running_mean", running_mean), ("running_var", running_var)):
+        if t is None and name.startswith("running"):
+            continue
+        E.require_gpu(t, what)
+        if t.shape != (C,) or not t.is_contiguous():
+            raise RuntimeError(f"{what}: {name} must be a contiguous [{C}] tensor, got {tuple(t.shape)}")
+    if (running_mean is None) != (running_var is None):
+        raise RuntimeError(f"{what}: running_mean and running_var come together")
+    if momentum is None:
+        raise NotImplementedError(f"{what}: momentum=None (the cumulative moving average) is not built")
+    if C < 1:
+        raise RuntimeError(f"{what}: y has no channel")
+    if B * N < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(y.shape)}")
+    rm = running_mean.detach() if running_mean is not None else None
+    rv = running_var.detach() if running_var is not None else None
+    z, stats = _BnActTrain.apply(y, bn_weight, bn_bias, rm, rv, float(momentum), float(eps), bool(relu))
+    return (z, stats) if return_stats else z
+
+
+_zero_bias = {}
+_counters = None            # the num_batches_tracked tensors of the open batch_counters() block
+
+
+def _zeros(cout, dev):
+    key = (cout, dev)
+    if key not in _zero_bias:
+        _zero_bias[key] = torch.zeros(cout, dtype=torch.float32, device=dev)
+    return _zero_bias[key]
+
+
+class batch_counters:
+    """with batch_counters(): every pointwise_bn_train inside adds its module's num_batches_tracked with one torch._foreach_add_ at the
+    end of the block (one launch per step) instead of one op per layer."""
+
+    def __enter__(self):
+        global _counters
+        self.outer, _counters = _counters, []
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        global _counters
+        mine, _counters = _counters, self.outer
+        if exc_type is None and mine:
+            if self.outer is not None:
+                self.outer.extend(mine)
+            else:
+                torch._foreach_add_(mine, 1)
+        return False
+
+
+def pointwise_bn_train(in0, in1, weight, bn, relu):
+    """One conv -> BatchNorm (-> ReLU) layer in training mode: the conv is pointwise_mlp_train without activation, with a cached zero bias
+    that needs no gradient (so no bias gradient is computed); `bn` is the nn.BatchNorm1d / 2d module, whose running statistics and
+    num_batches_tracked are updated as its own training forward would."""
+    if bn.momentum is None:
+        raise NotImplementedError("BatchNorm with momentum=None (the cumulative moving average) is not built on the HIP shared MLPs")
+    if not bn.affine:
+        raise NotImplementedError("BatchNorm without affine parameters is not built on the HIP shared MLPs")
+    E.require_gpu(weight, "pointwise_bn_train")
+    y = pointwise_mlp_train(in0, in1, weight, _zeros(weight.shape[0], weight.device), False)
+    track = bn.track_running_stats and bn.running_mean is not None
+    z = bn_act_train(y, bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None, bn.momentum, bn.eps,
+                     relu)
+    if track and bn.num_batches_tracked is not None:
+        if _counters is not None:
+            _counters.append(bn.num_batches_tracked)
+        else:
+            bn.num_batches_tracked.add_(1)
+    return z
+
+
+def train_layer_apply(in0, in1, layer, relu):
+    """One training layer, (weight, bias) or (weight, None, bn), on in0 (B,C0,N) and in1 (B,C1,N) or None."""
+    if len(layer) == 3:
+        return pointwise_bn_train(in0, in1, layer[0], layer[2], relu)
+    return pointwise_mlp_train(in0, in1, layer[0], layer[1], relu)
+
+
 class _GroupMax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
@@ -293,7 +435,8 @@ def group_max(x, return_arg=False):
 
 def sa_mlp_max_train(xyz, new_xyz, feats, idx, layers):
     """The training form of sa_mlp_max, with autograd through feats and the layers' parameters: xyz (B,N,3), new_xyz (B,M,3), feats (B,C,N)
-    or None, idx (B,M,ns) int32, layers: 1..3 of (weight, bias) raw parameters, ReLU after every layer -> (B, Cout, M).  The grouped
+    or None, idx (B,M,ns) int32, layers: 1..3 of (weight, bias) raw parameters or (weight, None, bn) with a BatchNorm module (batch
+    statistics over all B * M * ns grouped columns, padded duplicates included), ReLU after every layer -> (B, Cout, M).  The grouped
     tensor and every layer's activation live in HBM: group (grouping_operation) -> subtract the centre -> pointwise_mlp_train over the
     M * ns columns -> group_max.  The coordinates are constants of the graph."""
     from .pointnet2 import grouping_operation
@@ -319,14 +462,15 @@ def sa_mlp_max_train(xyz, new_xyz, feats, idx, layers):
     if not 1 <= len(layers) <= 3:
         raise RuntimeError(f"{what}: 1 to 3 layers, got {len(layers)}")
     cin = C + 3
-    for i, (w, b) in enumerate(layers):
+    for i, l in enumerate(layers):
+        w = l[0]
         if w.shape[0] < 1 or w.numel() != w.shape[0] * cin:
             raise RuntimeError(f"{what}: layer {i} has weight {tuple(w.shape)}, its input has {cin} channels")
         cin = w.shape[0]
     if B == 0 or M == 0:
         # nothing to launch: a correctly shaped result that still hangs on its inputs, so that backward gives them zero gradients
         out = torch.zeros((B, cin, M), dtype=torch.float32, device=xyz.device)
-        for t in [feats] + [p for l in layers for p in l]:
+        for t in [feats] + [p for l in layers for p in (l[:2] if len(l) == 2 else (l[0], l[2].weight, l[2].bias))]:
             if t is not None and t.requires_grad:
                 out = out + 0.0 * t.sum()
         return out
@@ -336,6 +480,6 @@ def sa_mlp_max_train(xyz, new_xyz, feats, idx, layers):
     if C:
         g = torch.cat([g, grouping_operation(feats.contiguous(), idx)], dim=1)
     x = g.reshape(B, C + 3, M * ns)
-    for w, b in layers:
-        x = pointwise_mlp_train(x, None, w, b, True)
+    for l in layers:
+        x = train_layer_apply(x, None, l, True)
     return group_max(x.reshape(B, cin, M, ns))

@@ -1,4 +1,5 @@
-"""Pointnet2MSG: the PointNet++ backbone of PointRCNN's RPN (reference: point_rcnn/lib/net/pointnet2_msg.py), inference only."""
+"""Pointnet2MSG: the PointNet++ backbone of PointRCNN's RPN (reference: point_rcnn/lib/net/pointnet2_msg.py).  It trains, with
+BatchNorm on the statistics of the batch, once pytorch_utils.enable_bn_training was called on a module above it (the RPN does)."""
 import torch.nn as nn
 
 from ..pointnet2_lib.pointnet2.pointnet2_modules import PointnetFPModule, PointnetSAModuleMSG

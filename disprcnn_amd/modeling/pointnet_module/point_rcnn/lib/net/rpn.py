@@ -1,8 +1,14 @@
-"""RPN: the first network of PointRCNN's 3D stage (reference: point_rcnn/lib/net/rpn.py), evaluation forward on HIP.
+"""RPN: the first network of PointRCNN's 3D stage (reference: point_rcnn/lib/net/rpn.py) on HIP.
 
 instance point cloud (B,N,3) -> Pointnet2MSG backbone -> per-point classification and box-regression heads -> ProposalLayer.
 The state-dict keys equal the reference's for the same cfg (the Dropout at index 1 of each head keeps the indices), so a reference
-checkpoint loads with strict=True.  No loss and no backward: a forward in training mode raises.
+checkpoint loads with strict=True.
+
+Training (the reference's _forward_train): forward(pts_input, rpn_cls_label, rpn_reg_label, matched_targets) ->
+({'rpn_cls', 'rpn_reg', 'backbone_xyz', 'backbone_features'}, {'rpn_loss_cls', 'rpn_loss_reg'}).  The backbone and the heads run their
+training forms (BatchNorm on the statistics of the batch: the RPN opts in with pytorch_utils.enable_bn_training), the heads' Dropout is
+torch's, the loss is PointRCNNLossComputation.  matched_targets: one object per image with len() instances and, optionally, the field
+'matched_idxs' (default zeros), concatenated to one entry per cloud.  Missing labels and RPN.FIXED raise NotImplementedError.
 """
 import math
 
@@ -12,8 +18,11 @@ import torch.nn as nn
 from disprcnn_amd.layers.rpn_proposals import points_depth
 
 from ..pointnet2_lib.pointnet2 import pytorch_utils as pt_utils
+from disprcnn_amd.layers import pn2_mlp
+
 from ..rpn.proposal_layer import ProposalLayer
 from .pointnet2_msg import Pointnet2MSG
+from .rpn_loss import PointRCNNLossComputation
 
 
 class RPN(nn.Module):
@@ -39,7 +48,12 @@ class RPN(nn.Module):
         self.rpn_cls_layer = head(rpn.CLS_FC, 1)
         self.rpn_reg_layer = head(rpn.REG_FC, reg_channel)
         self.proposal_layer = ProposalLayer(cfg, total_cfg)
+        try:
+            self.loss_evaluator = PointRCNNLossComputation(cfg)
+        except NotImplementedError:                        # a LOSS_CLS the eval network accepts: raised again when training starts
+            self.loss_evaluator = None
         self.init_weights()
+        pt_utils.enable_bn_training(self)
 
     def init_weights(self):
         if self.cfg.RPN.LOSS_CLS in ["SigmoidFocalLoss"]:
@@ -54,9 +68,27 @@ class RPN(nn.Module):
                 x = layer(x)
         return x
 
+    def _forward_train(self, pts_input, rpn_cls_label, rpn_reg_label, matched_targets):
+        if rpn_cls_label is None or rpn_reg_label is None or matched_targets is None:
+            raise NotImplementedError("RPN: the training forward needs rpn_cls_label, rpn_reg_label and matched_targets "
+                                      "(PointRCNN.generate_rpn_training_labels); without them only the evaluation forward runs: call .eval()")
+        if self.cfg.RPN.FIXED:
+            raise NotImplementedError("RPN.FIXED: a fixed RPN is not trained; call .eval()")
+        if self.loss_evaluator is None:
+            PointRCNNLossComputation(self.cfg)             # raises with the reason
+        with pn2_mlp.batch_counters():
+            backbone_xyz, backbone_features = self.backbone_net(pts_input)
+            rpn_cls = self.rpn_cls_layer(backbone_features).transpose(1, 2).contiguous()
+            rpn_reg = self.rpn_reg_layer(backbone_features).transpose(1, 2).contiguous()
+        ret_dict = {"rpn_cls": rpn_cls, "rpn_reg": rpn_reg, "backbone_xyz": backbone_xyz, "backbone_features": backbone_features}
+        dev = rpn_cls.device
+        matched_idxs = torch.cat([a.get_field("matched_idxs").to(dev) if a.has_field("matched_idxs")
+                                  else torch.zeros(len(a), dtype=torch.long, device=dev) for a in matched_targets])
+        return ret_dict, self.loss_evaluator(rpn_cls, rpn_reg, rpn_cls_label, rpn_reg_label, matched_idxs)
+
     def forward(self, pts_input, rpn_cls_label=None, rpn_reg_label=None, matched_targets=None):
         if self.training:
-            raise NotImplementedError("RPN: only the evaluation forward is implemented (no loss, no backward); call .eval()")
+            return self._forward_train(pts_input, rpn_cls_label, rpn_reg_label, matched_targets)
         with torch.no_grad():
             backbone_xyz, backbone_features = self.backbone_net(pts_input)                         # (B,N,3), (B,C,N)
             rpn_cls = self._head(self.rpn_cls_layer, backbone_features).transpose(1, 2).contiguous()   # (B,N,1)

@@ -10,7 +10,10 @@ so every index equals the reference's.
 
 In training mode an SA module without BatchNorm takes the materialising route (pn2_mlp.sa_mlp_max_train per scale, torch.cat over the
 scales) with autograd through the features and the layers' parameters; FPS, gather and ball query stay under no_grad, so the
-coordinates are constants of the graph.  A BatchNorm layer in training, and PointnetFPModule in training, raise.
+coordinates are constants of the graph.  A BatchNorm layer in training, and PointnetFPModule in training, raise, unless
+pytorch_utils.enable_bn_training was called on a module above them: then each layer is conv -> BatchNorm on the batch statistics -> ReLU
+(over all B * npoint * nsample grouped columns of an SA scale, as the reference's BatchNorm2d counts them), and the FP module is
+three_nn and the weights under no_grad -> three_interpolate with its backward -> the MLP, whose first layer takes its two inputs.
 """
 from typing import List
 
@@ -48,7 +51,7 @@ class PointnetSAModuleMSG(nn.Module):
 
     def forward(self, xyz, features=None, new_xyz=None):
         """xyz (B,N,3), features (B,C,N) or None -> new_xyz (B,npoint,3), new_features (B, sum of the scales' widths, npoint)."""
-        train = [m.train_layers() for m in self.mlps] if self.training else None          # raises for a BatchNorm layer
+        train = [m.train_layers() for m in self.mlps] if self.training else None          # raises for a BatchNorm layer that is not enabled
         if self.npoint is None:
             return None, self._forward_group_all(xyz, features, train)
         with torch.no_grad():
@@ -109,11 +112,14 @@ class PointnetFPModule(nn.Module):
     def __init__(self, *, mlp: List[int], bn: bool = True):
         super().__init__()
         self.mlp = pt_utils.SharedMLP(mlp, bn=bn)
+        self._bn_train = False                              # set by pytorch_utils.enable_bn_training
 
     def forward(self, unknown, known, unknow_feats, known_feats):
         """unknown (B,n,3), known (B,m,3), unknow_feats (B,C1,n) or None, known_feats (B,C2,m) -> (B, mlp[-1], n)."""
         if self.training:
-            raise NotImplementedError("PointnetFPModule: the HIP forward is inference only; call .eval()")
+            if not self._bn_train:
+                raise NotImplementedError("PointnetFPModule: the HIP forward is inference only; call .eval()")
+            return self._forward_train(unknown, known, unknow_feats, known_feats)
         with torch.no_grad():
             if known is not None:
                 dist, idx = pointnet2_utils.three_nn(unknown, known)
@@ -126,4 +132,20 @@ class PointnetFPModule(nn.Module):
             for layer in self.mlp:
                 x = pn2_mlp.pointwise_mlp(x, skip, layer.folded(), None, layer.relu)
                 skip = None
+        return x
+
+    def _forward_train(self, unknown, known, unknow_feats, known_feats):
+        layers = self.mlp.train_layers()
+        if known is not None:
+            with torch.no_grad():
+                dist, idx = pointnet2_utils.three_nn(unknown, known)
+                inv = 1.0 / (dist + 1e-8)
+                weight = inv / inv.sum(dim=2, keepdim=True)
+            x = pointnet2_utils.three_interpolate(known_feats.contiguous(), idx, weight)
+        else:
+            x = known_feats.expand(*known_feats.size()[0:2], unknown.size(1)).contiguous()
+        skip = unknow_feats
+        for holder, layer in zip(self.mlp, layers):
+            x = pn2_mlp.train_layer_apply(x, skip, layer, holder.relu)
+            skip = None
         return x

@@ -6,7 +6,9 @@ layers/pn2_mlp.py read it (BatchNorm folded in fp64 on the host, K-major on the 
 buffer changes.  Calling a holder directly does its one layer through `pointwise_mlp`.
 
 In training mode a layer without BatchNorm runs through `pn2_mlp.pointwise_mlp_train` with its raw parameters as autograd inputs (the
-eval arithmetic, plus the HIP backward); a layer with BatchNorm raises: batch statistics are not built.
+eval arithmetic, plus the HIP backward).  A layer with BatchNorm raises, unless `enable_bn_training` has been called on a module above
+it: then the layer is conv -> BatchNorm on the statistics of the batch (-> ReLU) through `pn2_mlp.pointwise_bn_train`, which updates
+the running statistics.  Batch-stat training is opt-in because only the RPN is trained that way; RCNNNet with USE_BN still refuses.
 """
 import torch.nn as nn
 
@@ -48,6 +50,7 @@ class _ConvBase(nn.Module):
             self.bn = batch_norm(out_size)
         self.relu = activation is not None
         self._fold = None
+        self._bn_train = False                              # set by enable_bn_training
 
     def _tensors(self):
         ts = [self.conv.weight, self.conv.bias]
@@ -73,9 +76,14 @@ class _ConvBase(nn.Module):
         return self._fold[1]
 
     def train_layer(self):
-        """(weight, bias): the raw parameters, as the training forms of layers/pn2_mlp.py take them."""
+        """(weight, bias), or (weight, None, bn) for a BatchNorm layer under enable_bn_training: the raw parameters, as the training forms
+        of layers/pn2_mlp.py take them.  A BatchNorm layer's fold is dropped: the training kernels write the running statistics through
+        raw pointers, which `folded()`'s version check cannot see."""
         if hasattr(self, "bn"):
-            raise NotImplementedError("BatchNorm in training mode: the HIP shared MLPs train without BatchNorm only (USE_BN = False)")
+            if not self._bn_train:
+                raise NotImplementedError("BatchNorm in training mode: the HIP shared MLPs train without BatchNorm only (USE_BN = False)")
+            self._fold = None
+            return self.conv.weight, None, self.bn.bn
         if self.conv.bias is None:
             raise NotImplementedError("a layer without bias in training mode is not supported by the HIP shared-MLP kernels")
         return self.conv.weight, self.conv.bias
@@ -87,7 +95,7 @@ class _ConvBase(nn.Module):
                 raise NotImplementedError("a shared MLP over grouped points runs through layers.pn2_mlp.sa_mlp_max")
             x = x.squeeze(3)
         if self.training:
-            y = pn2_mlp.pointwise_mlp_train(x, None, *self.train_layer(), self.relu)
+            y = pn2_mlp.train_layer_apply(x, None, self.train_layer(), self.relu)
         else:
             y = pn2_mlp.pointwise_mlp(x, None, self.folded(), None, self.relu)
         return y.unsqueeze(3) if squeeze else y
@@ -101,6 +109,15 @@ class Conv1d(_ConvBase):
 class Conv2d(_ConvBase):
     def __init__(self, in_size, out_size, *, activation="relu", bn=False, bias=True, preact=False, instance_norm=False):
         super().__init__(nn.Conv2d, BatchNorm2d, in_size, out_size, activation, bn, bias, preact, instance_norm)
+
+
+def enable_bn_training(module):
+    """Let every conv holder and every PointnetFPModule below `module` (itself included) train with BatchNorm on batch statistics.
+    -> module."""
+    for m in module.modules():
+        if hasattr(m, "_bn_train"):
+            m._bn_train = True
+    return module
 
 
 class SharedMLP(nn.Sequential):

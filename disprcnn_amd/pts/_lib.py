@@ -42,6 +42,11 @@ _SIGS = {
     "drc_pn2_pointwise_mlp_wgrad": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "drc_pn2_group_max_fwd": (_I, [_L, _I, _P, _P, _P, _P]),
     "drc_pn2_group_max_bwd": (_I, [_L, _I, _P, _P, _P, _P]),
+    "drc_pn2_bn_chunk": (_I, []),
+    "drc_pn2_bn_workspace_doubles": (_L, [_I, _I, _I]),
+    "drc_pn2_bn_stats": (_I, [_I, _I, _I, _P, _P, _F, _F, _P, _P, _P, _P]),
+    "drc_pn2_bn_apply_fwd": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "drc_pn2_bn_bwd": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "drc_rpn_points_depth": (_I, [_L, _P, _P, _P]),
     "drc_rpn_decode_proposals": (_I, [_L, _I, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
     "drc_rcnn_pool_canonical_fwd": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _F, _F, _P, _P, _P, _P, _P]),

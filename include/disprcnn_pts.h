@@ -152,6 +152,33 @@ int drc_pn2_group_max_fwd(int64_t rows, int ns, const float* x, float* out, int3
 int drc_pn2_group_max_bwd(int64_t rows, int ns, const float* gout, const int32_t* arg, float* gin, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * BatchNorm with batch statistics for the shared MLPs (pts/pn2_bn.hip): torch.nn.BatchNorm1d / 2d in training mode over an fp32
+ * activation [B, C, N], channel-major (N = M * nsample for an SA level: every grouped column counts, padded duplicates included).
+ * The statistic of channel c runs over its n = B * N values.  Every sum is fp64 in a fixed order: a grid of (column chunk, channel)
+ * workgroups writes partials into a caller-provided fp64 workspace and a second launch adds them in chunk order.  No atomics: the same
+ * bits run to run, which depend on the chunk length.  16-byte loads and stores when N % 4 == 0 and every tensor base is 16-byte aligned,
+ * scalar ones otherwise.  No allocation, no copy, no synchronisation; -1 bad arguments (n < 2, C < 1, B < 1, N < 1, a null pointer),
+ * -2 limits (C <= 65535).
+ * ------------------------------------------------------------------------------------- */
+/* The number of columns of the flattened (b, n) axis one partial sum covers. */
+int drc_pn2_bn_chunk(void);
+/* Doubles of workspace the two reducing entry points need: 2 * C * (ceil(B N / chunk) + 1); -1 for bad arguments. */
+int64_t drc_pn2_bn_workspace_doubles(int B, int C, int N);
+/* mean_invstd [2, C] <- the mean of y over (b, n) and 1 / sqrt(var + eps), var the biased variance, each rounded once from fp64.
+ * running_mean, running_var [C] (both null, or both given) are updated in place as torch does:
+ * r <- (1 - momentum) r + momentum * (mean | var * n / (n - 1)).  `workspace` need not be set. */
+int drc_pn2_bn_stats(int B, int C, int N, const float* y, double* workspace, float eps, float momentum, float* mean_invstd,
+                     float* running_mean, float* running_var, void* stream);
+/* z <- act(gamma (y - mean) invstd + beta), act = ReLU when relu != 0, else the identity; one pass, every element is written. */
+int drc_pn2_bn_apply_fwd(int B, int C, int N, int relu, const float* y, const float* mean_invstd, const float* gamma, const float* beta,
+                         float* z, void* stream);
+/* With g = gz (.) [z > 0] when relu != 0 (z may be null otherwise), xh = (y - mean) invstd, s1 = sum g, s2 = sum g xh over (b, n):
+ * gy <- gamma invstd (g - s1 / n - xh s2 / n), ggamma [C] <- s2, gbeta [C] <- s1 (each rounded once from fp64).  Two passes over the
+ * columns with the fixed-order sum of the partials between them.  Every element of gy is written. */
+int drc_pn2_bn_bwd(int B, int C, int N, int relu, const float* gz, const float* z, const float* y, const float* mean_invstd,
+                   const float* gamma, double* workspace, float* gy, float* ggamma, float* gbeta, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * PointRCNN RCNN stage (pts/rcnn_ops.hip; rcnn_net.py's ROI_SAMPLE_JIT eval branch, rcnn_inference.py).
  * ------------------------------------------------------------------------------------- */
 /* ROI pooling fused with the canonical transform, one workgroup per (cloud, ROI), in the layouts the RPN returns and the shared MLPs
