@@ -57,8 +57,8 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr int PV = 128;         // voxels per chunk plane of a slab (>= (rows + 2) * SX + the 4 columns lanes 28..31 over-read)
-constexpr int CPB = PV * 16;    // bytes per chunk plane
+constexpr int PV_ROWS = 128;    // voxels per chunk plane of a slab (>= (rows + 2) * SX + the 4 columns lanes 28..31 over-read)
+constexpr int PV_FLAT = 192;    // ... of the flat form (7 stacked rows, the last one up to column 8)
 constexpr int RING = 3;
 
 // RT rows x WT columns of the map make one 32-voxel MFMA tile: 1 x 28 (full-resolution maps, tiles along x), 2 x 14 and 4 x 7 (the
@@ -85,8 +85,22 @@ constexpr int RING = 3;
 // same instructions -- the sums are always computed, the layout selects the data and the offsets of the same two stores (the second one
 // is dropped by its offset in the rows layout).  drc_head_gather_rows_fwd adds T0[y-1] + (T1a[y] + T1b[y]) + T2[y+1] of the same column:
 // 16 B written + 16 read per voxel.
-template <int KW, bool CV, int RT = 1, int WT = 28, bool RES = false, bool Y32 = false, bool HEAD = false>
+// FLAT, written RT == 0 (the plain and the residual 32 -> 32 layer on 28-column maps: KW == 2, RT == 1, WT == 28, no Y32, no HEAD): a tile is not an
+// image row but 32 CONSECUTIVE voxels of the flattened (unit, row, x) order of a group of G units (p.dil bit 0x4000: G = 1, else 4), so all 32
+// MFMA columns of a tile work: 24.5 instead of 28 tiles per 28 x 28 plane.  Column c of a group = tiles 2c (wave pair r = 0) and 2c + 1: 64
+// voxels f = 64c .. 64c + 63, f = (n - n0) H W + y W + x; voxels past the group's last unit are masked like the ragged tiles of the row form.
+// The slab of a column stacks, at the row form's stride SX, the PADDED rows its voxels touch: from the row above the first voxel's to the row
+// below the last one's; at a unit seam the bottom halo row of unit n is at once the top halo row of unit n + 1 (both are stored zeros), followed
+// by the first map row of n + 1.  A lane's B-fragment address points at its own voxel's row of the stack, so the uniform tap immediates
+// (kh*SX + kw)*16 land on that voxel's true neighbours, and the inner loop is the row form's, instruction for instruction: same sums, same
+// order, same bits.  A chunk plane is 192 voxels: from H == 3 on a column touches at most 4 map rows in 2 units = 7 stacked rows, the last one
+// read up to column 8 (voxel 188); H == 1 | 2 reach 9 | 8 rows only for a column that starts in the last 7 voxels of a row, and a column
+// starts at a multiple of 64 voxels of a group of 28 | 56 | 112 | 224: x = 0, 8, 16, 24 (two units: 7 rows).  Staging and store offsets are
+// relative to the column's first unit (at most 3 units further: 32 bits).
+template <int KW, bool CV, int RT_ = 1, int WT = 28, bool RES = false, bool Y32 = false, bool HEAD = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void convs16_kernel(const drc_s16conv_params p) {
+    constexpr bool FL = RT_ == 0;               // flat tiles: no rows of the map, 32 consecutive voxels
+    constexpr int RT = FL ? 1 : RT_;
     static_assert(!HEAD || (KW == 2 && !CV && RT == 1 && !RES && !Y32), "the fused cout-1 head is a form of the 32 -> 32 full-resolution layer");
     static_assert(!CV || (KW == 4 && RT == 1 && WT == 28 && !RES && !Y32), "the cost-volume form: 64 virtual input channels, full-resolution rows, RS16 output");
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -100,14 +114,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     constexpr int CBI = KW / 2;                 // 32-channel input blocks
     constexpr int SROWS = RPW * RT + 2;
     static_assert(RT * WT <= 32, "tile shape");
+    static_assert(!FL || (KW == 2 && !CV && WT == 28 && !Y32 && !HEAD), "flat tiles: the plain / residual 32 -> 32 layer on 28-column maps");
+    constexpr int PV = FL ? PV_FLAT : PV_ROWS;  // voxels per chunk plane
+    constexpr int CPB = PV * 16;                // bytes per chunk plane
+    constexpr int NH = PV / 64;                 // 64-voxel pieces of a chunk plane: one LDS-DMA instruction each
     constexpr int SLAB = CBI * 8 * CPB;
-    constexpr int NL = CBI * 8 * (PV / 64) / 4; // LDS-DMA instructions per wave and slab
+    constexpr int NL = CBI * 8 * NH / 4;        // LDS-DMA instructions per wave and slab
     constexpr int OWN = 16 / KW;                // accumulator registers (couts per lane) a wave finishes
     constexpr int XW = 4096;                    // bytes a wave publishes per plane: its 16 accumulator registers
     constexpr int NR = RES ? 2 : 0;             // residual loads per step (hi, lo)
     constexpr int NS = 2;                       // stores per step (RS16 hi, lo | blocked fp32 x2)
     static_assert(!(Y32 && (KW != 2 || RES)), "the blocked fp32 output exists for the 32-channel layers without residual");
-    static_assert(RT == 1 ? SROWS * SX + 4 <= PV : (SROWS + 1) * SX + 4 <= PV, "slab plane too small (incl. the rows / columns the idle lanes over-read)");
+    static_assert(FL || (RT == 1 ? SROWS * SX + 4 <= PV : (SROWS + 1) * SX + 4 <= PV), "slab plane too small (incl. the rows / columns the idle lanes over-read)");
     char* ring = lds;
     char* xchg = lds + RING * SLAB;             // [2 parities][4 waves][XW]
     char* pbuf = xchg + 2 * 4 * XW;             // HEAD: [2 parities][2 tiles][XW] the K-slice-1 halves of P
@@ -183,7 +201,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         srcrow[h] = rr;
         srcx[h] = srcok[h] ? v - rr * SX : 0;
     }
-    const unsigned bfrag = (unsigned)(((k >> 1) * 8 + (k & 1) * 2 + g) * CPB + ((r * RT + rl) * SX + xl) * 16);     // hi; lo at + 4*CPB
+    const unsigned bfrag0 = (unsigned)(((k >> 1) * 8 + (k & 1) * 2 + g) * CPB);                                      // hi; lo at + 4*CPB
+    const unsigned bfrag = bfrag0 + (unsigned)(((r * RT + rl) * SX + xl) * 16);                                      // (flat: per column, Ctx::bf)
     const __attribute__((address_space(3))) char* ringl = (const __attribute__((address_space(3))) char*)ring;
     typedef const __attribute__((address_space(3))) f16x8 lds_frag;
 
@@ -194,29 +213,71 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // XCD-aware order: block b runs on XCD b % 8; the 32 blocks of an XCD take 32 consecutive columns of the units n % 8 == xcd, so that the
     // row tiles sharing halo rows meet in one L2
     const unsigned xcd = blockIdx.x & 7, qx = (blockIdx.x >> 3) / n_ct, per_xcd = (gridDim.x >> 3) / n_ct;
-    const unsigned cols_unit = (unsigned)n_yt * n_xt;
+    // flat: groups of G units take the place of the units (group gi -> XCD gi % 8), columns of 64 flattened voxels that of the row tiles
+    const int HW = H * W, Hp1 = H + 1;
+    const unsigned G = FL ? ((p.dil & 0x4000) ? 1u : 4u) : 1u;
+    const unsigned cols_unit = FL ? (G * (unsigned)HW + 63u) / 64u : (unsigned)n_yt * n_xt;
 
     // ---- the columns of this workgroup, in order; the pipeline below runs through them WITHOUT draining at a column's end: the first two
     // steps of a column publish / finalize the last planes of the previous one, the last two stage the first slabs of the next one.
-    struct Col { unsigned n; int y0, x0; bool valid; };
+    // (flat: n = the unit of the column's first voxel, (y0, x0) = that voxel, rem0 = its index in the unit, lim = voxels from there to the
+    // end of the group)
+    struct Col { unsigned n; int y0, x0; bool valid; int rem0, lim; };
     auto col_of = [&](unsigned it) __attribute__((always_inline)) {
         const unsigned j = it * per_xcd + qx;
         const unsigned nl = j / cols_unit;
         const unsigned rem = j - nl * cols_unit;
+        if constexpr (FL) {
+            Col c;
+            const unsigned n0 = (nl * 8 + xcd) * G;
+            const int gu = n0 < (unsigned)p.N ? (int)((unsigned)p.N - n0 < G ? (unsigned)p.N - n0 : G) : 0;      // units of this group
+            const int f0 = (int)rem * 64;
+            const int u0 = f0 / HW;
+            c.valid = f0 < gu * HW;
+            c.n = n0 + (unsigned)u0;
+            c.rem0 = f0 - u0 * HW;
+            c.lim = gu * HW - f0;
+            c.y0 = c.rem0 / WT;
+            c.x0 = c.rem0 - c.y0 * WT;
+            return c;
+        }
         const int yb = (int)(rem / n_xt), xt = (int)(rem - (unsigned)yb * n_xt);
         Col c;
         c.n = nl * 8 + xcd;
         c.valid = c.n < (unsigned)p.N;
         c.y0 = yb * RPW * RT;
         c.x0 = xt * TX;
+        c.rem0 = c.lim = 0;
         return c;
     };
     // staging source of a column: the unit's input as a buffer base + this lane's byte offsets of its two staged voxels (h = 0, 1); the
     // plane / channel-block / chunk offset of an instruction is a scalar (soffset)
-    struct Src { const char* a; unsigned v0, v1; };
+    struct Src { const char* a; unsigned v0, v1, v2, v3; };
     auto src_of = [&](const Col& c) __attribute__((always_inline)) {
         Src q;
         q.a = (const char*)p.x + (long)c.n * xnB;
+        q.v2 = q.v3 = 0u;
+        if constexpr (FL) {
+            // stacked row rr of the slab = padded row y0 + rr of the first unit, continued behind that unit's bottom halo row (which stands for
+            // the next unit's top one) with the next unit's padded rows 1 .. H + 1, and so on; rows below the one under the column's last
+            // voxel are not needed: dropped by their offset
+            const int el = c.rem0 + (c.lim < 64 ? c.lim : 64) - 1;                              // the last voxel, counted from the first unit's origin
+            const int du_l = (el >= HW) + (el >= 2 * HW) + (el >= 3 * HW);
+            const int rr_last = du_l * Hp1 + (el - du_l * HW) / WT - c.y0 + 2;
+            static_assert(NH <= 4, "pieces of a chunk plane");
+            unsigned vv[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int h = 0; h < NH; ++h) {
+                const int v = h * 64 + lane;
+                const int rr = v / SX, xs = v - rr * SX;
+                const int L = c.y0 + rr, M = L - 1;
+                const int uo = (M >= Hp1) + (M >= 2 * Hp1) + (M >= 3 * Hp1);
+                const unsigned off = (unsigned)((long)uo * xnB + (long)(L - uo * Hp1) * rowB + (long)xs * 16);
+                vv[h] = rr <= rr_last ? off : 0x80000000u;
+            }
+            q.v0 = vv[0]; q.v1 = vv[1]; q.v2 = vv[2]; q.v3 = vv[3];
+            return q;
+        }
         q.v0 = (unsigned)((long)(c.y0 + srcrow[0]) * rowB + (long)(c.x0 + srcx[0]) * 16);
         q.v1 = (unsigned)((long)(c.y0 + srcrow[1]) * rowB + (long)(c.x0 + srcx[1]) * 16);
         return q;
@@ -224,11 +285,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     auto stage = [&](const Src& q, int pl, int slot) __attribute__((always_inline)) {       // input plane pl of a column -> ring slot
         char* dst = ring + slot * SLAB;
         const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)q.a, 0, 0x7FFFFF00, 0x00020000);
-        const unsigned va[2] = {q.v0, q.v1};
+        const unsigned va[4] = {q.v0, q.v1, q.v2, q.v3};
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
             const int id = wave * NL + i;
-            const int cb = id >> 4, c = (id >> 1) & 7, h = id & 1;
+            // (flat: one channel block, NL a multiple of NH -- the piece h of an instruction is a constant, its chunk wave-uniform)
+            const int cb = FL ? 0 : id >> 4, c = FL ? wave * (NL / NH) + i / NH : (id >> 1) & 7, h = FL ? i % NH : id & 1;
             const int so = (int)((long)cb * xcbB + (long)(pl + 1) * planeB + (long)c * (Wp * 16));
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, LDS_PTR(dst + (cb * 8 + c) * CPB + h * 1024), 16, va[h], so, 0, 0);
         }
@@ -238,9 +300,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int hs_slotB = hrows ? 16 : 48;
     const long hs_planeB = (long)H * W * hs_slotB, hs_nB = (long)D * hs_planeB;    // HEAD: float [N][D][H][W][12]
     const bool hs_drop0 = hrows && g, hs_drop1 = hrows || g;                        // lanes whose first / second store is dropped by its offset
-    struct Ctx { char* y16b; char* y32b; const char* resb; char* hsb; unsigned o16, o32, ohs; bool ok; };
+    struct Ctx { char* y16b; char* y32b; const char* resb; char* hsb; unsigned o16, o32, ohs, bf; bool ok; };
     auto ctx_of = [&](const Col& c) __attribute__((always_inline)) {
         Ctx q;
+        q.bf = bfrag;
+        if constexpr (FL) {
+            // this lane's voxel: number 32 r + n_ of the column, du units behind the column's first one; a lane past the group's end is masked
+            // and reads (never stores) the slab's first voxel
+            q.hsb = (char*)p.w;
+            q.y32b = (char*)p.w;
+            q.ohs = q.o32 = 0u;
+            q.y16b = (char*)p.y16 + (long)c.n * ynB;
+            q.resb = p.res ? (const char*)p.res + (long)c.n * ynB : (const char*)p.w;
+            q.ok = r * 32 + n_ < c.lim;
+            const int e0 = q.ok ? c.rem0 + r * 32 + n_ : c.rem0;
+            const int du = (e0 >= HW) + (e0 >= 2 * HW) + (e0 >= 3 * HW);
+            const int e = e0 - du * HW;
+            const int yl = e / WT, xv = e - yl * WT;
+            q.bf = bfrag0 + (unsigned)(((du * Hp1 + yl - c.y0) * SX + xv) * 16);
+            q.o16 = (unsigned)((long)du * ynB + (long)ct * xcbB + planeB + (long)(yl + 1) * rowB + (long)(k * 2 + g) * (Wp * 16) + (long)(xv + 1) * 16);
+            return q;
+        }
         q.hsb = HEAD ? (char*)p.head + (long)c.n * hs_nB : (char*)p.w;
         q.ohs = (unsigned)(((long)(c.y0 + r * RT + rl) * W + (c.x0 + xl)) * hs_slotB + (hrows ? 0 : g * 32));
         q.y16b = p.y16 ? (char*)p.y16 + (long)c.n * ynB : (char*)p.w;
@@ -356,6 +436,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             q.a = nxt ? s_next.a : s_cur.a;
             q.v0 = nxt ? s_next.v0 : s_cur.v0;
             q.v1 = nxt ? s_next.v1 : s_cur.v1;
+            q.v2 = nxt ? s_next.v2 : s_cur.v2;
+            q.v3 = nxt ? s_next.v3 : s_cur.v3;
             int pl = nxt ? tp - Dw : tp;
             pl = pl < D ? pl : D;                       // phantom planes (and the over-staging behind the last column): the zero halo plane D + 1
             stage(q, pl, (J + 2) % 3);
@@ -493,7 +575,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         };
         if constexpr (COMPUTE) {
             constexpr bool K0 = KIND != 2, K2 = KIND != 1;          // taps kd = 0 (plane t+1 exists), kd = 2 (plane t-1 exists)
-            const __attribute__((address_space(3))) char* sb = ringl + J * SLAB + bfrag;
+            const __attribute__((address_space(3))) char* sb = ringl + J * SLAB + (FL ? cx_cur.bf : bfrag);
             f16x8 bh[2], bl[2];
             bh[0] = *(lds_frag*)(sb);
             bl[0] = *(lds_frag*)(sb + 4 * CPB);
@@ -600,10 +682,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     og.flush(p.ovf);
 }
 
+// flat tiles: the columns of a launch (groups of 4 units, or of 1 with dil bit 0x4000; the last group may be short but is enumerated whole)
+inline long s16_flat_columns(const drc_s16conv_params& p) {
+    const long G = (p.dil & 0x4000) ? 1 : 4;
+    return (p.N + G - 1) / G * ((G * p.H * p.W + 63) / 64);
+}
+constexpr long FLAT_MIN_COLUMNS = 2048;       // below: the row form (eight columns per workgroup; 256 Config-A ROIs have 3136)
+
 template <int KW, bool CV, int RT, int WT, bool RES, bool Y32, bool HEAD = false>
 int launch2(const drc_s16conv_params& p, hipStream_t stream) {
     constexpr int CBI = KW / 2;
-    constexpr int SLAB = CBI * 8 * CPB;
+    constexpr bool FLAT = RT == 0;
+    constexpr int SLAB = CBI * 8 * (FLAT ? PV_FLAT : PV_ROWS) * 16;
     constexpr int XW = 4096;
     constexpr size_t lds = CV ? (size_t)s16cv::LDS_BYTES : RING * SLAB + 2 * 4 * XW + (HEAD ? 2 * 2 * XW : 0);
     static_assert(lds <= 160 * 1024, "LDS");
@@ -612,8 +702,8 @@ int launch2(const drc_s16conv_params& p, hipStream_t stream) {
         (void)hipFuncSetAttribute((const void*)convs16_kernel<KW, CV, RT, WT, RES, Y32, HEAD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_done = true;
     }
-    constexpr int rows = (4 / KW) * RT;
-    const long columns = (long)p.N * ((p.H + rows - 1) / rows) * ((p.W + WT - 1) / WT);
+    constexpr int rows = FLAT ? 1 : (4 / KW) * RT;
+    const long columns = FLAT ? s16_flat_columns(p) : (long)p.N * ((p.H + rows - 1) / rows) * ((p.W + WT - 1) / WT);
     // one block per CU (the weights take the register file); a multiple of 8 so that every XCD runs the same number
     const int n_ct = p.cout / 32;
     long blocks = 256;                                   // column workers x cout tiles (the tiles of a worker side by side on its XCD)
@@ -648,6 +738,22 @@ extern "C" int drc_conv3d_k3_s16_supported(int cin, int cout, int D, int H, int 
     return D > 0 && H > 0 && W > 0;
 }
 
+// The form a parameter block's launch takes (host code, no launch): 0 = row tiles; 1 | 4 = flat tiles in groups of that many units (the plain
+// and the residual 32 -> 32 layer on 28-column maps, at least FLAT_MIN_COLUMNS columns, offsets of four units inside 32 bits); -4: flat
+// tiles were asked for (dil bit 0x2000) where the form does not exist.  dil bit 0x1000 keeps the row form.
+extern "C" int drc_conv3d_k3_s16_flat(const drc_s16conv_params* pp) {
+    if (!pp) return -1;
+    const drc_s16conv_params& p = *pp;
+    const bool forced = p.dil & 0x2000;
+    const long unit16 = (long)(p.D + 2) * (p.H + 2) * (p.W + 2) * 128;
+    const bool can = p.cin == 32 && p.cout == 32 && p.W == 28 && p.D > 0 && p.H > 0 && p.N > 0 && p.x && p.y16 && !p.y32 && !p.head && !p.left && !p.right &&
+                     4 * unit16 < 0x7FFFFF00L;
+    if (p.dil & 0x1000) return forced ? -1 : 0;
+    if (!can) return forced ? -4 : 0;
+    if (!forced && s16_flat_columns(p) < FLAT_MIN_COLUMNS) return 0;
+    return (p.dil & 0x4000) ? 1 : 4;
+}
+
 extern "C" int drc_conv3d_k3_s16_fwd(const drc_s16conv_params* pp, void* stream) {
     if (!pp) return -1;
     const drc_s16conv_params& p = *pp;
@@ -673,6 +779,9 @@ extern "C" int drc_conv3d_k3_s16_fwd(const drc_s16conv_params* pp, void* stream)
     hipStream_t s = (hipStream_t)stream;
     if (drc_conv3d_k3_s16_wide(pp)) return drc_conv3d_k3_s16_wide_fwd(pp, stream);      // the cost-volume form at large batches: two tiles per wave (convs16w.hip)
     if (cv) return launch<4, true>(p, s);
+    const int flat = drc_conv3d_k3_s16_flat(pp);
+    if (flat < 0) return flat;
+    if (flat) return p.res ? launch2<2, false, 0, 28, true, false>(p, s) : launch2<2, false, 0, 28, false, false>(p, s);
     if (p.W <= 7) return p.cin == 32 ? launch<2, false, 4, 7>(p, s) : launch<4, false, 4, 7>(p, s);
     if (p.W <= 14) return p.cin == 32 ? launch<2, false, 2, 14>(p, s) : launch<4, false, 2, 14>(p, s);
     return p.cin == 32 ? launch<2, false>(p, s) : launch<4, false>(p, s);

@@ -1388,6 +1388,7 @@ HEAD_FUSED = {"enabled": True}       # eval, split-f16 regressor: classif[0] + t
 LASTCONV_S16 = {"enabled": True}     # eval, split-f16 2D schedule: lastconv[0] (320 -> 128) as three chained split-f16 launches over the concat's parts (runtime._ws2d_s16)
 S16 = {"enabled": True}       # eval: the stride-1 3x3x3 layers at full resolution on the f16 matrix cores in split arithmetic (convs16.hip)
 HEAD_ROWS = {"enabled": True}        # eval, fused heads on 28-column maps: the head launches sum the width taps (rows layout, 16 B per voxel) and ONE gather adds the three heads into cost3; False: the 12-float slots + a gather per head (A/B switch, read at every forward)
+FLAT_TILES = {"enabled": True, "group": 4}   # the plain / residual 32 -> 32 layers on 28-column maps: MFMA tiles of 32 consecutive voxels of a group of `group` (4 or 1) units instead of one 28-voxel row (convs16.hip; the library keeps small launches on rows); False: row tiles; "force": True asks for flat tiles whatever the launch's size (A/B switch, read at every run())
 CV_WIDE = {"enabled": True}   # eval, large batches: the cost-volume layer with two rows per work item (convs16w.hip); False: convs16.hip's one-row form (A/B switch, read at every run())
 
 
@@ -1646,6 +1647,14 @@ class ConvPlanS16:
     def _wide(self):
         return self.kind == "s1" and self._wide_ok and bool(CV_WIDE["enabled"])
 
+    def _flat_bits(self):
+        """FLAT_TILES as the library's `dil` bits of drc_conv3d_k3_s16_fwd: 0x1000 row tiles, 0x2000 flat tiles forced, 0x4000 groups of one unit."""
+        if self.kind != "s1" or self.cv:
+            return 0
+        if not FLAT_TILES["enabled"]:
+            return 0x1000
+        return (0x2000 if FLAT_TILES.get("force") else 0) | (0x4000 if int(FLAT_TILES["group"]) == 1 else 0)
+
     def run(self, x16, w16, scale, shift, y16=None, y32=None, res=None, left=None, right=None, lo4=0, head=None, head_rows=False):
         """head = (packed 32 -> 1 weights of s16.pack_head_weight_s16, S buffer fp32 of >= N*D*H*W*12 floats): the layer is classif[0] of a
         head, its output is not stored, the partial sums of the cout-1 layer behind it are (head_gather finishes it).  head_rows (W == 28): the
@@ -1679,7 +1688,7 @@ class ConvPlanS16:
                              _ptr(res.storage) if res is not None else None, _ptr(y16.storage) if y16 is not None else None,
                              _ptr(y32.storage) if y32 is not None else None, _ptr(left.storage) if self.cv else None,
                              _ptr(right.storage) if self.cv else None, self.N, self.D, self.H, self.W, self.cin, self.cout, int(self.relu), int(lo4),
-                             0x800 if (self.cv and self.kind == "s1" and not CV_WIDE["enabled"]) else int(self.dil),   # (the library's experiment bit of the 3D layers' unused `dil` field: keep the one-row kernel)
+                             0x800 if (self.cv and self.kind == "s1" and not CV_WIDE["enabled"]) else int(self.dil) | self._flat_bits(),   # (the library's switch bits of the 3D layers' unused `dil` field: keep the one-row kernel; row / flat tiles)
                              _ptr(head[1]) if head is not None else None, _ptr(head[0]) if head is not None else None, _ovf_ptr(), int(bool(head_rows)))
         dev = self.device
         if TIMING is not None:

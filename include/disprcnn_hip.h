@@ -364,7 +364,9 @@ typedef struct drc_s16conv_params {
     int32_t N, D, H, W;
     int32_t cin, cout, relu;
     int32_t lo4;         /* cost-volume variant: disparity of volume slice 0 (mindisp/4) */
-    int32_t dil;         /* drc_conv2d_k3_s16_fwd only: dilation (0 or 1: none; 2) */
+    int32_t dil;         /* drc_conv2d_k3_s16_fwd only: dilation (0 or 1: none; 2).  drc_conv3d_k3_s16_fwd reads its high bits as switches: 0x800 keeps
+                            the one-row cost-volume kernel; 0x1000 keeps row tiles, 0x2000 asks for flat tiles (-4 where that form does not exist),
+                            0x4000: flat tiles in groups of one unit instead of four (drc_conv3d_k3_s16_flat below) */
     float* head;         /* drc_conv3d_k3_s16_fwd, cin = cout = 32, W % 28 == 0, D >= 6, y16 = y32 = res = NULL: the layer is classif[0] of a head and
                             its output is not stored; the in-plane partial sums of the 32 -> 1 convolution behind it (classif[2],
                             stackhourglass.py:78-88) are: float [N][D][H][W][12], S[kh*3+kw] of the SOURCE voxel summed over the depth taps
@@ -387,6 +389,13 @@ int drc_conv3d_k3_s16_fwd(const drc_s16conv_params* p, void* stream);
  * the two-row kernel: the cost-volume form, W > 14, H even, at least 1024 two-row items (smaller launches keep the finer items; dil bit
  * 0x800 forces them); drc_conv3d_k3_s16_wide_fwd launches it for any cost-volume block. */
 int drc_conv3d_k3_s16_wide(const drc_s16conv_params* p);
+/* Flat tiles (round 12): the plain and the residual 32 -> 32 layer on 28-column maps (cin = cout = 32, W == 28, y16 output, any D, H, N) with
+ * an MFMA tile of 32 consecutive voxels of the flattened (unit, row, x) order of a group of four units (or of one) instead of one 28-voxel image
+ * row: 24.5 instead of 28 tiles per 28 x 28 plane, the same sums in the same order -- bit-identical to the row tiles, halo and guard word
+ * included.  drc_conv3d_k3_s16_flat (host code, no launch) says which form drc_conv3d_k3_s16_fwd gives a parameter block: 0 = row tiles,
+ * 1 | 4 = flat tiles in groups of that many units (chosen from 2048 flat columns of 64 voxels on, smaller launches keep the row tiles; needs
+ * four units' bytes below 2^31), < 0: flat tiles forced (dil bit 0x2000) on a block that has no such form. */
+int drc_conv3d_k3_s16_flat(const drc_s16conv_params* p);
 int drc_conv3d_k3_s16_wide_fwd(const drc_s16conv_params* p, void* stream);
 /* The second half of a fused head (p->head above): cost[n][z][y][x] = (res ? res[..] : 0) + scale * sum_{kh,kw} S[n][z][y+kh-1][x+kw-1][kh*3+kw]
  * (sources outside the volume contribute zero: the convolution's zero padding); cost, res: dense float [N][D][H][W] (res = the previous
