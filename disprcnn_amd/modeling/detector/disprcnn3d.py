@@ -14,7 +14,15 @@ The 3D stage (reference :34-43, :281-282, :317-323).  MODEL.DET3D_ON builds `pcn
 left / right results and `lr_targets["left"]` (one calibration per image) to it: the left results come back with `box3d`, `scores_3d` (and
 `random` with the RCNN).  MODEL.DISPNET_ON false builds no PSMNet: the incoming left results must then carry `disparity` and `mask`
 already -- the offline form every shipped rpn.yaml / rcnn.yaml uses -- and the images are not read.  Both flags together give 3D boxes from
-a stereo pair in one call.  Training with DET3D_ON (PointRCNN's targets, losses and backward) is not built and raises.
+a stereo pair in one call.
+
+Training with DET3D_ON (reference :209-264): after remove_low_score_rois and -- only with DISPNET_ON -- the PSMNet part, the left / right
+results and the left targets go to `pcnet`, whose losses are added when SOLVER.TRAIN_PC.  The MAX_ROI_FOR_TRAINING truncation follows the
+reference: DISPNET's limit when the disparity net trains, PCNET's (20 where the cfg lacks the key) when it is in eval mode and `pcnet`
+trains.  The `disparity` field PSMNet leaves on the results is detached and the points kernels have no backward: no gradient reaches
+PSMNet from the 3D losses (the reference's clouds are not differentiable with respect to the disparities either: they are drawn by index
+on the host).  Training with DET3D_ON and SOLVER.TRAIN_PC false raises before any input is read: PointRCNN's training forward would run
+only to have its losses dropped.
 """
 from types import SimpleNamespace
 
@@ -194,9 +202,24 @@ class DispRCNN3D(nn.Module):
     def _forward_train(self, left_images, right_images, left_result, right_result, left_targets):
         losses = {}
         left_result, right_result = self.remove_low_score_rois(left_result, right_result)
+        if self.dispnet_on:
+            left_result, right_result = self._forward_train_dispnet(left_images, right_images, left_result, right_result, left_targets, losses)
+        if self.det3d_on:
+            _, pc_loss = self.pcnet(left_result, right_result, left_targets)
+            if self.cfg.SOLVER.TRAIN_PC:
+                losses.update(pc_loss)
+        return losses
+
+    def _forward_train_dispnet(self, left_images, right_images, left_result, right_result, left_targets, losses):
+        """The PSMNet part of the training forward: adds disp_loss to `losses` (with SOLVER.TRAIN_PSM) and returns the (possibly truncated)
+        results, the left ones with their detached `disparity` field."""
         left, right, targets, masks = self.prepare_psmnet_input_and_target(left_images, right_images, left_result, right_result, left_targets)
-        max_rois = self.cfg.MODEL.DISPNET.MAX_ROI_FOR_TRAINING
-        if self.dispnet.training and left.shape[0] > max_rois:
+        max_rois = None
+        if self.dispnet.training:
+            max_rois = self.cfg.MODEL.DISPNET.MAX_ROI_FOR_TRAINING
+        elif self.det3d_on and self.pcnet.training:
+            max_rois = getattr(getattr(self.cfg.MODEL, "PCNET", None), "MAX_ROI_FOR_TRAINING", 20)
+        if max_rois is not None and left.shape[0] > max_rois:
             left, right, targets, masks = left[:max_rois], right[:max_rois], targets[:max_rois], masks[:max_rois]
             left_result, right_result = self._truncate(left_result, max_rois), self._truncate(right_result, max_rois)
         if left.shape[0] > 0:
@@ -214,19 +237,20 @@ class DispRCNN3D(nn.Module):
         out3 = output[2] if isinstance(output, (list, tuple)) else output
         for o3, lr in zip(torch.split(out3.detach(), [len(r) for r in left_result]), left_result):
             lr.add_field("disparity", o3)
-        return losses
+        return left_result, right_result
 
     def forward(self, lr_images, lr_result, lr_targets=None):
-        if self.training and self.det3d_on:
-            raise NotImplementedError("DispRCNN3D with MODEL.DET3D_ON: PointRCNN training (SOLVER.TRAIN_PC: targets, losses, backward) is "
-                                      "not built; call .eval(), or train the disparity stage with DET3D_ON false")
-        if self.training and not self.dispnet_on:
+        if self.training and self.det3d_on and not getattr(self.cfg.SOLVER, "TRAIN_PC", False):
+            raise NotImplementedError("DispRCNN3D with MODEL.DET3D_ON and SOLVER.TRAIN_PC false: PointRCNN's training forward would run only "
+                                      "to have its losses dropped; set SOLVER.TRAIN_PC, or call .eval()")
+        if self.training and not self.dispnet_on and not self.det3d_on:
             raise NotImplementedError("DispRCNN3D without MODEL.DISPNET_ON has nothing to train")
         left_result, right_result = self.remove_illegal_detections(lr_result["left"], lr_result["right"])
         if self.training:
             if lr_targets is None:
                 raise ValueError("DispRCNN3D in training mode needs lr_targets (reference disprcnn3d.py:303)")
-            return self._forward_train(lr_images["left"], lr_images["right"], left_result, right_result, lr_targets["left"])
+            images = lr_images if self.dispnet_on else {"left": None, "right": None}      # without the PSMNet the images are not read
+            return self._forward_train(images["left"], images["right"], left_result, right_result, lr_targets["left"])
         if self.det3d_on and lr_targets is None:
             raise ValueError("DispRCNN3D with MODEL.DET3D_ON needs lr_targets in evaluation too: lr_targets['left'] holds one BoxList with a "
                              "'calib' field (or one calibration) per image")

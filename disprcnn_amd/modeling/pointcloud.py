@@ -13,6 +13,15 @@ rotates and centres the drawn points.  The host reads the per-ROI counts once --
 The draw.  The reference reseeds NumPy's global legacy generator to 0 before each choice and each shuffle, so the chosen indices
 depend only on the count n and npoints.  Here a private ``np.random.RandomState(0)`` per ROI gives the same stream and leaves NumPy's
 global state alone (the reference leaves it reseeded to 0); the arrays are cached by n.
+
+The training form (``InstancePointCloud.train_clouds``; reference :97-187 process_input with back_project's fix_seed=False): the mask
+threshold is the caller's (MODEL.POINTRCNN.MASK_THRESH), depth has no lower clamp (a pixel of negative depth falls to the z > 0
+filter), the draw is not reseeded but reads a generator `rng` -- NumPy's global legacy generator by default, as the reference, or any
+``RandomState`` -- with the reference's calls in the reference's order (``draw_choice_train`` per ROI, then ``draw_augmentation``), and
+kernel B applies the augmentation in the reference's order: z clamped at `max_depth`, times `scale`, x negated when flipped, the
+rotation by the angle negated when flipped, the mean subtracted.  The returned `rot_angle` is the signed angle that was used.  The
+counts still come to the host in the call's one read; a caller may append int64 slots to that buffer and fill them on the device before
+the read (PointRCNN puts the 2D matcher's indices there).
 """
 import numpy as np
 import torch
@@ -35,6 +44,30 @@ def draw_choice(n, npoints):
         choice = np.concatenate((np.arange(n), choice))
     np.random.RandomState(0).shuffle(choice)
     return choice
+
+
+def draw_choice_train(n, npoints, rng=None):
+    """back_project's draw without fix_seed (point_rcnn.py:59-73) for n kept points, read from `rng` (default: the numpy.random module,
+    as the reference): choice, then shuffle.  int64 [npoints] indices."""
+    if n <= 0:
+        raise ValueError("draw_choice_train needs n >= 1")
+    rng = np.random if rng is None else rng
+    if n > npoints:
+        choice = rng.choice(n, npoints, replace=False)
+    else:
+        choice = rng.choice(n, npoints - n, replace=True)
+        choice = np.concatenate((np.arange(n), choice))
+    rng.shuffle(choice)
+    return choice
+
+
+def draw_augmentation(rng=None):
+    """process_input's draws after the clouds (point_rcnn.py:145-154): uniform(0.95, 1.05) for the scale, then random() < 0.5 for the
+    flip -> (scale, flip)."""
+    rng = np.random if rng is None else rng
+    scale = float(rng.uniform(0.95, 1.05))
+    flip = bool(rng.random() < 0.5)
+    return scale, flip
 
 
 class InstancePointCloud:
@@ -66,6 +99,16 @@ class InstancePointCloud:
     def __call__(self, left_result, right_result, calibs):
         """left_result / right_result: per-image BoxLists (left ones carry 'disparity' [R,S,S] and 'mask' [R,1,M,M]); calibs: one Calib
         (or P2/P3 calibration object) per image.  Returns pts [R,npoints,3] (centred), pts_mean [R,3], rot_angle [R] (float64)."""
+        return self._run(left_result, right_result, calibs, None)[:3]
+
+    def train_clouds(self, left_result, right_result, calibs, rng=None, augment=True, tail=0, fill_tail=None):
+        """The training form (see the module's docstring).  rng: numpy.random (default) or a RandomState; augment: draw a scale and a flip
+        after the clouds (False with RPN.FIXED: scale 1, no flip, no draw).  tail / fill_tail: `tail` int64 slots appended to the buffer
+        the counts are read through; fill_tail(view) is called once, before the read, to fill them on the device.
+        Returns pts [R,npoints,3], pts_mean [R,3], rot_angle [R] (float64, signed), scale, flip, the tail as a CPU int64 tensor."""
+        return self._run(left_result, right_result, calibs, dict(rng=rng, augment=augment, tail=int(tail), fill_tail=fill_tail))
+
+    def _run(self, left_result, right_result, calibs, train):
         counts = [len(lr) for lr in left_result]
         R = sum(counts)
         if len(right_result) != len(left_result) or len(calibs) < len(left_result):
@@ -73,7 +116,7 @@ class InstancePointCloud:
         dev = left_result[0].bbox.device if left_result else torch.device("cuda")
         if R == 0:
             return (torch.empty(0, self.npoints, 3, device=dev), torch.empty(0, 3, device=dev),
-                    torch.empty(0, dtype=torch.float64, device=dev))
+                    torch.empty(0, dtype=torch.float64, device=dev), 1.0, False, torch.empty(0, dtype=torch.int64))
         if not dev.type == "cuda":
             raise RuntimeError("InstancePointCloud: expected CUDA/HIP boxes on an MI355X; the HIP path has no CPU fallback")
         parts = [i for i, c in enumerate(counts) if c]
@@ -115,14 +158,19 @@ class InstancePointCloud:
         roi_i = torch.cat([integer_roi_boxes(lb, rb), hw_d], dim=1).contiguous()
         roi_f = torch.cat([lb, cam_d], dim=1).contiguous()
 
-        info = torch.empty(2 * R + 1, dtype=torch.int64, device=dev)
+        tail = train["tail"] if train else 0
+        info = torch.empty(2 * R + 1 + tail, dtype=torch.int64, device=dev)
+        if tail:
+            train["fill_tail"](info[2 * R + 1:])
         stream = E._stream_ptr(dev)
         ws = self._workspace(dev, 0)
         L = _lib.lib()
+        kernel_a, name_a = (L.drc_instance_points_train_fwd, "drc_instance_points_train_fwd") if train else \
+            (L.drc_instance_points_fwd, "drc_instance_points_fwd")
         for _ in range(2):                      # a second pass only when the boxes outgrow the cached workspace
-            st = L.drc_instance_points_fwd(E._ptr(disp), S, E._ptr(roi_i), E._ptr(roi_f), E._ptr(mask), M, self.mask_padding,
-                                           self.mask_threshold, R, E._ptr(info), E._ptr(ws), ws.numel(), stream)
-            _lib.check(st, "drc_instance_points_fwd")
+            st = kernel_a(E._ptr(disp), S, E._ptr(roi_i), E._ptr(roi_f), E._ptr(mask), M, self.mask_padding,
+                          self.mask_threshold, R, E._ptr(info), E._ptr(ws), ws.numel(), stream)
+            _lib.check(st, name_a)
             info_h = info.cpu()
             if int(info_h[2 * R]) <= ws.numel():
                 break
@@ -132,17 +180,31 @@ class InstancePointCloud:
         if min(n_kept) == 0:
             raise EOFError("mask is nonvalid")
 
-        choice = torch.from_numpy(np.stack([self.choice(n) for n in n_kept])).pin_memory().to(dev, non_blocking=True)
+        scale, flip = 1.0, False
+        if train:
+            rng = train["rng"]
+            choice = np.stack([draw_choice_train(n, self.npoints, rng).astype(np.int32) for n in n_kept])
+            if train["augment"]:
+                scale, flip = draw_augmentation(rng)
+        else:
+            choice = np.stack([self.choice(n) for n in n_kept])
+        choice = torch.from_numpy(choice).pin_memory().to(dev, non_blocking=True)
         pts = torch.empty(R, self.npoints, 3, dtype=torch.float32, device=dev)
         mean = torch.empty(R, 3, dtype=torch.float32, device=dev)
         rot = torch.empty(R, dtype=torch.float64, device=dev)
         src = torch.empty(R, self.npoints, dtype=torch.int32, device=dev)
-        st = L.drc_instance_points_gather_fwd(E._ptr(disp), S, E._ptr(roi_i), E._ptr(roi_f), E._ptr(roi_d), R, E._ptr(info), E._ptr(ws),
-                                              E._ptr(choice), self.npoints, self.max_depth, E._ptr(pts), E._ptr(mean), E._ptr(rot),
-                                              E._ptr(src), stream)
-        _lib.check(st, "drc_instance_points_gather_fwd")
+        if train:
+            st = L.drc_instance_points_gather_train_fwd(E._ptr(disp), S, E._ptr(roi_i), E._ptr(roi_f), E._ptr(roi_d), R, E._ptr(info),
+                                                        E._ptr(ws), E._ptr(choice), self.npoints, self.max_depth, scale, int(flip),
+                                                        E._ptr(pts), E._ptr(mean), E._ptr(rot), E._ptr(src), stream)
+            _lib.check(st, "drc_instance_points_gather_train_fwd")
+        else:
+            st = L.drc_instance_points_gather_fwd(E._ptr(disp), S, E._ptr(roi_i), E._ptr(roi_f), E._ptr(roi_d), R, E._ptr(info), E._ptr(ws),
+                                                  E._ptr(choice), self.npoints, self.max_depth, E._ptr(pts), E._ptr(mean), E._ptr(rot),
+                                                  E._ptr(src), stream)
+            _lib.check(st, "drc_instance_points_gather_fwd")
         self.last_src_pix = src
-        return pts, mean, rot
+        return pts, mean, rot, scale, flip, info_h[2 * R + 1:].clone()
 
     @staticmethod
     def rotate_back(pts, rot_angle):

@@ -20,6 +20,9 @@ _SIGS = {
     "drc_pts_version": (C.c_char_p, []),
     "drc_instance_points_fwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _F, _I, _P, _P, _L, _P]),
     "drc_instance_points_gather_fwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P]),
+    "drc_instance_points_train_fwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _F, _I, _P, _P, _L, _P]),
+    "drc_instance_points_gather_train_fwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _F, _F, _I, _P, _P, _P, _P, _P]),
+    "drc_match_targets_fwd": (_I, [_I, _I, _P, _P, _P, _P, _I, _F, _F, _P, _P, _P]),
     "drc_pn2_furthest_point_sampling": (_I, [_I, _I, _I, _P, _P, _P, _I, _P]),
     "drc_pn2_gather_points": (_I, [_I, _I, _I, _I, _P, _P, _P, _P]),
     "drc_pn2_ball_query": (_I, [_I, _I, _I, _F, _I, _P, _P, _P, _P]),
@@ -57,6 +60,7 @@ _SIGS = {
     "drc_rcnn_pool_target_fwd": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P,
                                       _P, _P, _P, _P, _P]),
     "drc_rpn_to_camera_fwd": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "drc_camera_to_rpn_fwd": (_I, [_I, _I, _P, _F, _I, _P, _P, _P, _P]),
     "drc_train_scratch_doubles": (_I, []),
     "drc_rpn_point_labels": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "drc_bin_reg_targets": (_I, [_L, _I, _P, _P, _P, _P, _P, _P, _P]),

@@ -9,6 +9,10 @@
 // meshgrid(x, y)), a ballot + LDS scan compacts the flat image index of each kept pixel.  The host reads the counts once,
 // builds the draw, and kernel B recomputes the chosen points (the same device function, so bit-identical to what A kept),
 // rotates them and subtracts a fixed-order mean.
+//
+// The training form (process_input + back_project with fix_seed=False, point_rcnn.py:97-187) is the same two kernels with TRAIN set:
+// depth without the lower clamp (pixels of negative depth fall to the z > 0 filter), and in kernel B the augmentation in the
+// reference's order: clamp at max_depth, times `scale`, x negated when flipped, the rotation by the angle negated when flipped.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -58,9 +62,12 @@ __device__ __forceinline__ float roi_disparity(const float* __restrict__ d, int 
     return (v / (float)S * (float)wd + (float)b.x1) - (float)b.x1p;
 }
 
-// depth_roi = fuxb / (disp + 1e-6) (Tensor.__rtruediv__ = reciprocal * fuxb), clamp(min=1.0) keeping NaN (point_rcnn.py:218-219)
+// depth_roi = fuxb / (disp + 1e-6) (Tensor.__rtruediv__ = reciprocal * fuxb), clamp(min=1.0) keeping NaN (point_rcnn.py:218-219);
+// TRAIN: process_input's depth (:132-133), which has no clamp
+template <bool TRAIN>
 __device__ __forceinline__ float roi_depth(const float* __restrict__ d, int S, const RoiBox& b, int y, int x, float fuxb) {
     const float z = (1.f / (roi_disparity(d, S, b, y, x) + 1e-6f)) * fuxb;
+    if (TRAIN) return z;
     return z < 1.f ? 1.f : z;
 }
 
@@ -108,6 +115,7 @@ __device__ __forceinline__ int64_t roi_offset(const int32_t* __restrict__ roi_i,
     return off;
 }
 
+template <bool TRAIN>
 __global__ __launch_bounds__(kA) void instance_points_kernel(const float* __restrict__ disp, int S, const int32_t* __restrict__ roi_i,
                                                             const float* __restrict__ roi_f, const float* __restrict__ mask, int M, int pad,
                                                             float thresh, int R, int64_t* __restrict__ info, int32_t* __restrict__ ws,
@@ -133,11 +141,12 @@ __global__ __launch_bounds__(kA) void instance_points_kernel(const float* __rest
     const bool write = total <= ws_cap;
 
     // back_project's rule (:37-43): multiply by the mask only when it is non-empty and the masked depth has a positive pixel.
-    // Depth is >= 1 (or NaN) inside the box and 0 outside, so that is "the mask meets the box at a pixel of non-NaN depth".
+    // Depth is >= 1 (or NaN) inside the box and 0 outside, so that is "the mask meets the box at a pixel of non-NaN depth"; in the
+    // training form it is "a masked box pixel has positive depth".
     int hit = 0;
     for (int64_t t = tid; t < area && !hit; t += kA) {
         const int x = xlo + (int)(t / hh), y = ylo + (int)(t % hh);
-        if (masker_at(prob, M, pad, q, y, x, b.H, b.W, thresh)) hit = roi_depth(d, S, b, y, x, fuxb) > 0.f;
+        if (masker_at(prob, M, pad, q, y, x, b.H, b.W, thresh)) hit = roi_depth<TRAIN>(d, S, b, y, x, fuxb) > 0.f;
     }
     const int use_mask = __syncthreads_or(hit);
 
@@ -147,7 +156,7 @@ __global__ __launch_bounds__(kA) void instance_points_kernel(const float* __rest
         int keep = 0, x = 0, y = 0;
         if (t < area) {
             x = xlo + (int)(t / hh); y = ylo + (int)(t % hh);
-            float z = roi_depth(d, S, b, y, x, fuxb);
+            float z = roi_depth<TRAIN>(d, S, b, y, x, fuxb);
             if (use_mask) z = z * (float)masker_at(prob, M, pad, q, y, x, b.H, b.W, thresh);
             keep = z > 0.f;
         }
@@ -172,12 +181,13 @@ __global__ __launch_bounds__(kA) void instance_points_kernel(const float* __rest
     }
 }
 
+template <bool TRAIN>
 __global__ __launch_bounds__(kB) void instance_points_gather_kernel(const float* __restrict__ disp, int S, const int32_t* __restrict__ roi_i,
                                                                    const float* __restrict__ roi_f, const double* __restrict__ roi_d, int R,
                                                                    const int64_t* __restrict__ info, const int32_t* __restrict__ ws,
                                                                    const int32_t* __restrict__ choice, int npoints, float max_depth,
                                                                    float* __restrict__ pts, float* __restrict__ mean, double* __restrict__ rot,
-                                                                   int32_t* __restrict__ src_pix) {
+                                                                   int32_t* __restrict__ src_pix, float scale, int flip) {
     __shared__ float red[3][kB];
     const int r = blockIdx.x, tid = threadIdx.x;
     const RoiBox b = load_box(roi_i, r);
@@ -188,7 +198,8 @@ __global__ __launch_bounds__(kB) void instance_points_gather_kernel(const float*
     if (n <= 0) return;                             // the caller raises before launching on a ROI without a point
     // rotate_pc_along_y: centre in fp32 ((x1 + x2) / 2 - W/2), atan2 in fp64 against the fp64 focal length, cos/sin cast to fp32
     const float cw = (bf[0] + bf[2]) / 2.f - half_w0;
-    const double ang = atan2((double)cw, roi_d[r]);
+    double ang = atan2((double)cw, roi_d[r]);
+    if (TRAIN && flip) ang = -ang;                  // rotator.rot_angle *= -1 (point_rcnn.py:161)
     const float c = (float)cos(ang), s = (float)sin(ang), ns = (float)(-sin(ang));
     float* out = pts + (int64_t)r * npoints * 3;
     float sx = 0.f, sy = 0.f, sz = 0.f;
@@ -197,11 +208,15 @@ __global__ __launch_bounds__(kB) void instance_points_gather_kernel(const float*
         j = (j >= 0 && j < n) ? j : 0;
         const int p = ws[off + j];
         const int y = p / b.W, x = p - y * b.W;
-        const float z = roi_depth(d, S, b, y, x, fuxb);
+        const float z = roi_depth<TRAIN>(d, S, b, y, x, fuxb);
         // img_to_rect (calib.py:103-110), then clamp(z, max=max_depth) (point_rcnn.py:81)
-        const float px = (((float)x - cu) * z) / fu + tx;
-        const float py = (((float)y - cv) * z) / fv + ty;
-        const float pz = z > max_depth ? max_depth : z;
+        float px = (((float)x - cu) * z) / fu + tx;
+        float py = (((float)y - cv) * z) / fv + ty;
+        float pz = z > max_depth ? max_depth : z;
+        if (TRAIN) {                                // pts * scale, then x = -x (point_rcnn.py:145-156)
+            px *= scale; py *= scale; pz *= scale;
+            if (flip) px = -px;
+        }
         // [x, z] @ [[c, -s], [s, c]]^T
         const float rx = px * c + pz * ns;
         const float rz = px * s + pz * c;
@@ -236,7 +251,17 @@ extern "C" int drc_instance_points_fwd(const float* disp, int S, const int32_t* 
     if (R < 0 || S <= 0 || M <= 0 || pad < 0 || ws_cap < 0) return -2;
     if (R == 0) return 0;
     if (!disp || !roi_i || !roi_f || !mask || !info || (ws_cap > 0 && !ws)) return -1;
-    hipLaunchKernelGGL(instance_points_kernel, dim3((unsigned)R), dim3(kA), 0, (hipStream_t)stream, disp, S, roi_i, roi_f, mask, M, pad,
+    hipLaunchKernelGGL(instance_points_kernel<false>, dim3((unsigned)R), dim3(kA), 0, (hipStream_t)stream, disp, S, roi_i, roi_f, mask, M, pad,
+                       thresh, R, info, ws, ws_cap);
+    return (int)hipGetLastError();
+}
+
+extern "C" int drc_instance_points_train_fwd(const float* disp, int S, const int32_t* roi_i, const float* roi_f, const float* mask, int M, int pad,
+                                             float thresh, int R, int64_t* info, int32_t* ws, int64_t ws_cap, void* stream) {
+    if (R < 0 || S <= 0 || M <= 0 || pad < 0 || ws_cap < 0) return -2;
+    if (R == 0) return 0;
+    if (!disp || !roi_i || !roi_f || !mask || !info || (ws_cap > 0 && !ws)) return -1;
+    hipLaunchKernelGGL(instance_points_kernel<true>, dim3((unsigned)R), dim3(kA), 0, (hipStream_t)stream, disp, S, roi_i, roi_f, mask, M, pad,
                        thresh, R, info, ws, ws_cap);
     return (int)hipGetLastError();
 }
@@ -247,7 +272,18 @@ extern "C" int drc_instance_points_gather_fwd(const float* disp, int S, const in
     if (R < 0 || S <= 0 || npoints <= 0) return -2;
     if (R == 0) return 0;
     if (!disp || !roi_i || !roi_f || !roi_d || !info || !ws || !choice || !pts || !mean || !rot) return -1;
-    hipLaunchKernelGGL(instance_points_gather_kernel, dim3((unsigned)R), dim3(kB), 0, (hipStream_t)stream, disp, S, roi_i, roi_f, roi_d, R,
-                       info, ws, choice, npoints, max_depth, pts, mean, rot, src_pix);
+    hipLaunchKernelGGL(instance_points_gather_kernel<false>, dim3((unsigned)R), dim3(kB), 0, (hipStream_t)stream, disp, S, roi_i, roi_f, roi_d, R,
+                       info, ws, choice, npoints, max_depth, pts, mean, rot, src_pix, 1.f, 0);
+    return (int)hipGetLastError();
+}
+
+extern "C" int drc_instance_points_gather_train_fwd(const float* disp, int S, const int32_t* roi_i, const float* roi_f, const double* roi_d, int R,
+                                                    const int64_t* info, const int32_t* ws, const int32_t* choice, int npoints, float max_depth,
+                                                    float scale, int flip, float* pts, float* mean, double* rot, int32_t* src_pix, void* stream) {
+    if (R < 0 || S <= 0 || npoints <= 0) return -2;
+    if (R == 0) return 0;
+    if (!disp || !roi_i || !roi_f || !roi_d || !info || !ws || !choice || !pts || !mean || !rot) return -1;
+    hipLaunchKernelGGL(instance_points_gather_kernel<true>, dim3((unsigned)R), dim3(kB), 0, (hipStream_t)stream, disp, S, roi_i, roi_f, roi_d, R,
+                       info, ws, choice, npoints, max_depth, pts, mean, rot, src_pix, scale, flip ? 1 : 0);
     return (int)hipGetLastError();
 }

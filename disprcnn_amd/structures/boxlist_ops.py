@@ -1,6 +1,7 @@
 """BoxList operations of the 2D stage.  Reference: disprcnn/structures/boxlist_ops.py:11-96,178-217 -- boxlist_nms,
-double_view_boxlist_nms (left and right views suppressed separately, the kept sets intersected), remove_small_boxes, cat_boxlist.
-NMS itself runs in libdisprcnn_hip.so (layers/nms.py); index bookkeeping is torch plumbing."""
+double_view_boxlist_nms (left and right views suppressed separately, the kept sets intersected), remove_small_boxes, cat_boxlist, and
+boxlist_iou (:101-136).  NMS itself runs in libdisprcnn_hip.so (layers/nms.py); index bookkeeping is torch plumbing.  boxlist_iou is plain
+torch: PointRCNN's training input takes its IoUs inside the matching kernel (layers/match2d.py), whose comparator this function is."""
 import torch
 
 from ..layers import nms as _box_nms, nms_pair as _box_nms_pair, nms_pair_sorted_joint as _box_nms_joint
@@ -47,6 +48,19 @@ def double_view_boxlist_nms(left_boxlist, right_boxlist, nms_thresh, max_proposa
 def remove_small_boxes(boxlist, min_size):
     wh = boxlist.xywh()
     return boxlist[((wh[:, 2] >= min_size) & (wh[:, 3] >= min_size)).nonzero().squeeze(1)]
+
+
+def boxlist_iou(boxlist1, boxlist2):
+    """IoU of every box of boxlist1 [N] with every box of boxlist2 [M] (xyxy, the legacy +1 pixel convention) -> [N,M]."""
+    if boxlist1.size != boxlist2.size:
+        raise RuntimeError("boxlists should have same image size, got {}, {}".format(boxlist1, boxlist2))
+    area1, area2 = boxlist1.area(), boxlist2.area()
+    box1, box2 = boxlist1.bbox, boxlist2.bbox
+    lt = torch.max(box1[:, None, :2], box2[:, :2])
+    rb = torch.min(box1[:, None, 2:], box2[:, 2:])
+    wh = (rb - lt + 1).clamp(min=0)
+    inter = wh[:, :, 0] * wh[:, :, 1]
+    return inter / (area1[:, None] + area2 - inter)
 
 
 def cat_boxlist(bboxes):

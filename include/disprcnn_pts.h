@@ -45,6 +45,25 @@ int drc_instance_points_gather_fwd(const float* disp, int S, const int32_t* roi_
                                    const int64_t* info, const int32_t* ws, const int32_t* choice, int npoints, float max_depth,
                                    float* pts, float* mean, double* rot, int32_t* src_pix, void* stream);
 
+/* The training forms (PointRCNN.process_input + back_project with fix_seed=False): the same two kernels, same arguments and layouts.
+ * drc_instance_points_train_fwd: depth = fuxb / (disp + 1e-6) without the lower clamp at 1, so a pixel of negative depth is dropped by
+ * the z > 0 filter; the mask is applied when a masked box pixel has positive depth.
+ * drc_instance_points_gather_train_fwd: after the clamp at max_depth the point is multiplied by `scale`, x is negated when `flip`, and
+ * the rotation angle is negated when `flip`; rot[r] is the signed angle that was used. */
+int drc_instance_points_train_fwd(const float* disp, int S, const int32_t* roi_i, const float* roi_f, const float* mask, int M, int pad,
+                                  float thresh, int R, int64_t* info, int32_t* ws, int64_t ws_cap, void* stream);
+int drc_instance_points_gather_train_fwd(const float* disp, int S, const int32_t* roi_i, const float* roi_f, const double* roi_d, int R,
+                                         const int64_t* info, const int32_t* ws, const int32_t* choice, int npoints, float max_depth,
+                                         float scale, int flip, float* pts, float* mean, double* rot, int32_t* src_pix, void* stream);
+
+/* drc_match_targets_fwd: PointRCNN.match_targets_to_proposals for all images in one launch.  boxes [R,4] left proposals (xyxy), span
+ * [R,2] int32 = (first, count) of the ground truths of the proposal's image in gt [G,4] (xyxy) and gt_rows [G,row] (the targets' 3D
+ * boxes).  IoU with TO_REMOVE = 1 in fp32 as boxlist_iou, the max over the ground truths (ties to the lowest index), then
+ * Matcher(high, low, allow_low_quality_matches=False): matched [R] int64 = the index within the image, -1 below `low`, -2 below `high`;
+ * out_rows [R,row] = gt_rows at the index clamped at 0 (zeros when the image has no ground truth, where matched is -1). */
+int drc_match_targets_fwd(int R, int G, const float* boxes, const int32_t* span, const float* gt, const float* gt_rows, int row,
+                          float high, float low, int64_t* matched, float* out_rows, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * PointNet++ operator set (pointnet2_lib/pointnet2/src/pointnet2_api.cpp).  Layouts as the reference's *_gpu.cu.
  * ------------------------------------------------------------------------------------- */
@@ -309,6 +328,11 @@ int drc_focal_elementwise(int64_t n, const float* logits, const float* targets, 
  * Nothing is launched when B = 0 or N = M = 0; with only one of N, M zero the other part is still written. */
 int drc_rpn_to_camera_fwd(int B, int N, int M, const float* xyz, const float* boxes, const float* mean, const double* rot, float* xyz_cam,
                           float* depth, float* boxes_cam, void* stream);
+
+/* drc_camera_to_rpn_fwd (frame_ops_train.hip): its twin, the way in.  xyz [B,K,3] camera-frame points of cloud b -> out [B,K,3] in that cloud's frame: times
+ * `scale`, x negated when `flip`, rotated about y by rot[b] (fp64, the signed angle of the gather kernel), minus mean[b]. */
+int drc_camera_to_rpn_fwd(int B, int K, const float* xyz, float scale, int flip, const float* mean, const double* rot, float* out,
+                          void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * KITTI object scoring (pts/kitti_eval.hip; the KITTI devkit's evaluate_object.cpp): 2D, AOS, BEV and 3D precision at 41 recall samples.
