@@ -58,7 +58,7 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 namespace {
 
 constexpr int PV_ROWS = 128;    // voxels per chunk plane of a slab (>= (rows + 2) * SX + the 4 columns lanes 28..31 over-read)
-constexpr int PV_FLAT = 192;    // ... of the flat form (7 stacked rows, the last one up to column 8)
+constexpr int PV_FLAT = 192;    // ... of the flat form on 28-column maps (7 stacked rows, the last one up to column 8)
 constexpr int RING = 3;
 
 // RT rows x WT columns of the map make one 32-voxel MFMA tile: 1 x 28 (full-resolution maps, tiles along x), 2 x 14 and 4 x 7 (the
@@ -85,7 +85,8 @@ constexpr int RING = 3;
 // same instructions -- the sums are always computed, the layout selects the data and the offsets of the same two stores (the second one
 // is dropped by its offset in the rows layout).  drc_head_gather_rows_fwd adds T0[y-1] + (T1a[y] + T1b[y]) + T2[y+1] of the same column:
 // 16 B written + 16 read per voxel.
-// FLAT, written RT == 0 (the plain and the residual 32 -> 32 layer on 28-column maps: KW == 2, RT == 1, WT == 28, no Y32, no HEAD): a tile is not an
+// FLAT, written RT == 0 (the plain and the residual 32 -> 32 layer on 28-column maps: KW == 2, WT == 28, no Y32, no HEAD; the 64 -> 64
+// form on 14-column maps is described behind this paragraph): a tile is not an
 // image row but 32 CONSECUTIVE voxels of the flattened (unit, row, x) order of a group of G units (p.dil bit 0x4000: G = 1, else 4), so all 32
 // MFMA columns of a tile work: 24.5 instead of 28 tiles per 28 x 28 plane.  Column c of a group = tiles 2c (wave pair r = 0) and 2c + 1: 64
 // voxels f = 64c .. 64c + 63, f = (n - n0) H W + y W + x; voxels past the group's last unit are masked like the ragged tiles of the row form.
@@ -97,6 +98,13 @@ constexpr int RING = 3;
 // read up to column 8 (voxel 188); H == 1 | 2 reach 9 | 8 rows only for a column that starts in the last 7 voxels of a row, and a column
 // starts at a multiple of 64 voxels of a group of 28 | 56 | 112 | 224: x = 0, 8, 16, 24 (two units: 7 rows).  Staging and store offsets are
 // relative to the column's first unit (at most 3 units further: 32 bits).
+// FLAT, KW == 4, WT == 14 (the plain and the residual 64 -> 64 layer on 14-column maps, conv2 of the hourglasses, whose row tiles are
+// 2 x 14): all four waves split K, so a workgroup has ONE tile and a column is 32 consecutive voxels f = 32c .. 32c + 31 of a group of G units
+// (dil bit 0x4000: G = 1, 0x8000: 8, else 4; the host sets exactly one).  Everything above holds with 32 for 64: two channel blocks are staged
+// (chunks 0..15 over the four waves), rows are stacked at SX = 16, and a tile touches at most 4 map rows in 2 units from H == 3 on = 7 stacked
+// rows = 112 voxels, inside the row form's chunk plane of 128 (8 rows; H == 2 reaches 8 rows).  The host walks every column of a launch and
+// refuses the form where one would need a ninth row or a fourth unit behind its first (s16_flat_half_fits).  The epilogue stores half a chunk
+// per wave, the row form's KW == 4 rule.  LDS 3 x 32 + 32 KB and 8 LDS-DMA instructions per wave and slab, as the row form.
 template <int KW, bool CV, int RT_ = 1, int WT = 28, bool RES = false, bool Y32 = false, bool HEAD = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void convs16_kernel(const drc_s16conv_params p) {
     constexpr bool FL = RT_ == 0;               // flat tiles: no rows of the map, 32 consecutive voxels
@@ -114,8 +122,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     constexpr int CBI = KW / 2;                 // 32-channel input blocks
     constexpr int SROWS = RPW * RT + 2;
     static_assert(RT * WT <= 32, "tile shape");
-    static_assert(!FL || (KW == 2 && !CV && WT == 28 && !Y32 && !HEAD), "flat tiles: the plain / residual 32 -> 32 layer on 28-column maps");
-    constexpr int PV = FL ? PV_FLAT : PV_ROWS;  // voxels per chunk plane
+    static_assert(!FL || (((KW == 2 && WT == 28) || (KW == 4 && WT == 14)) && !CV && !Y32 && !HEAD), "flat tiles: the plain / residual 32 -> 32 layer on 28-column maps, 64 -> 64 on 14-column maps");
+    constexpr int FV = 32 * RPW;                // flat: voxels per column (one tile per wave set)
+    constexpr int PV = FL && KW == 2 ? PV_FLAT : PV_ROWS;  // voxels per chunk plane (flat, 14-column maps: 8 stacked rows of 16 fit the row form's plane)
     constexpr int CPB = PV * 16;                // bytes per chunk plane
     constexpr int NH = PV / 64;                 // 64-voxel pieces of a chunk plane: one LDS-DMA instruction each
     constexpr int SLAB = CBI * 8 * CPB;
@@ -213,10 +222,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // XCD-aware order: block b runs on XCD b % 8; the 32 blocks of an XCD take 32 consecutive columns of the units n % 8 == xcd, so that the
     // row tiles sharing halo rows meet in one L2
     const unsigned xcd = blockIdx.x & 7, qx = (blockIdx.x >> 3) / n_ct, per_xcd = (gridDim.x >> 3) / n_ct;
-    // flat: groups of G units take the place of the units (group gi -> XCD gi % 8), columns of 64 flattened voxels that of the row tiles
+    // flat: groups of G units take the place of the units (group gi -> XCD gi % 8), columns of FV flattened voxels that of the row tiles
     const int HW = H * W, Hp1 = H + 1;
-    const unsigned G = FL ? ((p.dil & 0x4000) ? 1u : 4u) : 1u;
-    const unsigned cols_unit = FL ? (G * (unsigned)HW + 63u) / 64u : (unsigned)n_yt * n_xt;
+    const unsigned G = FL ? ((p.dil & 0x4000) ? 1u : (KW == 4 && (p.dil & 0x8000)) ? 8u : 4u) : 1u;
+    const unsigned cols_unit = FL ? (G * (unsigned)HW + (unsigned)(FV - 1)) / (unsigned)FV : (unsigned)n_yt * n_xt;
 
     // ---- the columns of this workgroup, in order; the pipeline below runs through them WITHOUT draining at a column's end: the first two
     // steps of a column publish / finalize the last planes of the previous one, the last two stage the first slabs of the next one.
@@ -231,7 +240,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             Col c;
             const unsigned n0 = (nl * 8 + xcd) * G;
             const int gu = n0 < (unsigned)p.N ? (int)((unsigned)p.N - n0 < G ? (unsigned)p.N - n0 : G) : 0;      // units of this group
-            const int f0 = (int)rem * 64;
+            const int f0 = (int)rem * FV;
             const int u0 = f0 / HW;
             c.valid = f0 < gu * HW;
             c.n = n0 + (unsigned)u0;
@@ -261,7 +270,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             // stacked row rr of the slab = padded row y0 + rr of the first unit, continued behind that unit's bottom halo row (which stands for
             // the next unit's top one) with the next unit's padded rows 1 .. H + 1, and so on; rows below the one under the column's last
             // voxel are not needed: dropped by their offset
-            const int el = c.rem0 + (c.lim < 64 ? c.lim : 64) - 1;                              // the last voxel, counted from the first unit's origin
+            const int el = c.rem0 + (c.lim < FV ? c.lim : FV) - 1;                              // the last voxel, counted from the first unit's origin
             const int du_l = (el >= HW) + (el >= 2 * HW) + (el >= 3 * HW);
             const int rr_last = du_l * Hp1 + (el - du_l * HW) / WT - c.y0 + 2;
             static_assert(NH <= 4, "pieces of a chunk plane");
@@ -289,8 +298,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
             const int id = wave * NL + i;
-            // (flat: one channel block, NL a multiple of NH -- the piece h of an instruction is a constant, its chunk wave-uniform)
-            const int cb = FL ? 0 : id >> 4, c = FL ? wave * (NL / NH) + i / NH : (id >> 1) & 7, h = FL ? i % NH : id & 1;
+            // (flat: NL a multiple of NH -- the piece h of an instruction is a constant, its channel block and chunk wave-uniform)
+            const int fc = wave * (NL / NH) + i / NH;
+            const int cb = FL ? (CBI == 1 ? 0 : fc >> 3) : id >> 4, c = FL ? (CBI == 1 ? fc : fc & 7) : (id >> 1) & 7, h = FL ? i % NH : id & 1;
             const int so = (int)((long)cb * xcbB + (long)(pl + 1) * planeB + (long)c * (Wp * 16));
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, LDS_PTR(dst + (cb * 8 + c) * CPB + h * 1024), 16, va[h], so, 0, 0);
         }
@@ -305,7 +315,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         Ctx q;
         q.bf = bfrag;
         if constexpr (FL) {
-            // this lane's voxel: number 32 r + n_ of the column, du units behind the column's first one; a lane past the group's end is masked
+            // this lane's voxel: number 32 r + n_ of the column (KW == 4: r == 0), du units behind the column's first one; a lane past the group's end is masked
             // and reads (never stores) the slab's first voxel
             q.hsb = (char*)p.w;
             q.y32b = (char*)p.w;
@@ -318,7 +328,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const int e = e0 - du * HW;
             const int yl = e / WT, xv = e - yl * WT;
             q.bf = bfrag0 + (unsigned)(((du * Hp1 + yl - c.y0) * SX + xv) * 16);
-            q.o16 = (unsigned)((long)du * ynB + (long)ct * xcbB + planeB + (long)(yl + 1) * rowB + (long)(k * 2 + g) * (Wp * 16) + (long)(xv + 1) * 16);
+            // (the row form's rule: KW == 2 a whole chunk per wave, KW == 4 half a chunk)
+            const int och = KW == 2 ? k * 2 + g : (k >> 1) * 2 + g, ohalf = KW == 2 ? 0 : (k & 1) * 8;
+            q.o16 = (unsigned)((long)du * ynB + (long)ct * xcbB + planeB + (long)(yl + 1) * rowB + (long)och * (Wp * 16) + (long)(xv + 1) * 16 + ohalf);
             return q;
         }
         q.hsb = HEAD ? (char*)p.head + (long)c.n * hs_nB : (char*)p.w;
@@ -682,18 +694,47 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     og.flush(p.ovf);
 }
 
-// flat tiles: the columns of a launch (groups of 4 units, or of 1 with dil bit 0x4000; the last group may be short but is enumerated whole)
-inline long s16_flat_columns(const drc_s16conv_params& p) {
-    const long G = (p.dil & 0x4000) ? 1 : 4;
-    return (p.N + G - 1) / G * ((G * p.H * p.W + 63) / 64);
-}
 constexpr long FLAT_MIN_COLUMNS = 2048;       // below: the row form (eight columns per workgroup; 256 Config-A ROIs have 3136)
+constexpr long FLAT_HALF_GROUP = 8;           // the 64 -> 64 form on 14-column maps: units per group where the caller names none
+constexpr long FLAT_HALF_MIN_COLUMNS = 1176;  // ... and its lower bound in columns of 32 voxels: 192 half-resolution Config-A ROIs, the smallest batch measured where a worker runs fewer columns (10 against 11)
+
+// flat tiles: units per group -- dil bit 0x4000: 1; the 32 -> 32 form: else 4; the 64 -> 64 form: 0x8000: 8, 0x10000: 4, else FLAT_HALF_GROUP
+inline long s16_flat_group(const drc_s16conv_params& p) {
+    if (p.dil & 0x4000) return 1;
+    if (p.cin != 64) return 4;
+    return (p.dil & 0x8000) ? 8 : (p.dil & 0x10000) ? 4 : FLAT_HALF_GROUP;
+}
+// ... and the columns of a launch (64 voxels, 32 in the 64 -> 64 form; the last group may be short but is enumerated whole)
+inline long s16_flat_columns(const drc_s16conv_params& p) {
+    const long G = s16_flat_group(p), FV = p.cin == 64 ? 32 : 64;
+    return (p.N + G - 1) / G * ((G * p.H * p.W + FV - 1) / FV);
+}
+// The 64 -> 64 form stages a column into the row form's chunk plane of 128 voxels = 8 stacked rows of 16, and counts units from the column's
+// first one with three compares.  Whether every column of a launch stays inside both is decided here, by walking the columns of a whole group
+// and of the short last one exactly as the kernel's col_of / src_of do (H = 1 | 2 can reach a fourth unit or a ninth row, depending on where
+// the columns of a group of G units start).
+inline bool s16_flat_half_fits(long N, long G, long H) {
+    const long HW = H * 14, Hp1 = H + 1;
+    const long tail = N % G;
+    for (int pass = 0; pass < 2; ++pass) {
+        const long gu = pass == 0 ? (N >= G ? G : 0) : tail;
+        for (long f0 = 0; f0 < gu * HW; f0 += 32) {
+            const long u0 = f0 / HW, rem0 = f0 - u0 * HW, y0 = rem0 / 14;
+            const long lim = gu * HW - f0;
+            const long el = rem0 + (lim < 32 ? lim : 32) - 1;
+            const long du_l = el / HW;
+            const long rr_last = du_l * Hp1 + (el - du_l * HW) / 14 - y0 + 2;
+            if (du_l > 3 || rr_last > 7) return false;
+        }
+    }
+    return true;
+}
 
 template <int KW, bool CV, int RT, int WT, bool RES, bool Y32, bool HEAD = false>
 int launch2(const drc_s16conv_params& p, hipStream_t stream) {
     constexpr int CBI = KW / 2;
     constexpr bool FLAT = RT == 0;
-    constexpr int SLAB = CBI * 8 * (FLAT ? PV_FLAT : PV_ROWS) * 16;
+    constexpr int SLAB = CBI * 8 * (FLAT && KW == 2 ? PV_FLAT : PV_ROWS) * 16;
     constexpr int XW = 4096;
     constexpr size_t lds = CV ? (size_t)s16cv::LDS_BYTES : RING * SLAB + 2 * 4 * XW + (HEAD ? 2 * 2 * XW : 0);
     static_assert(lds <= 160 * 1024, "LDS");
@@ -738,20 +779,23 @@ extern "C" int drc_conv3d_k3_s16_supported(int cin, int cout, int D, int H, int 
     return D > 0 && H > 0 && W > 0;
 }
 
-// The form a parameter block's launch takes (host code, no launch): 0 = row tiles; 1 | 4 = flat tiles in groups of that many units (the plain
-// and the residual 32 -> 32 layer on 28-column maps, at least FLAT_MIN_COLUMNS columns, offsets of four units inside 32 bits); -4: flat
-// tiles were asked for (dil bit 0x2000) where the form does not exist.  dil bit 0x1000 keeps the row form.
+// The form a parameter block's launch takes (host code, no launch): 0 = row tiles; 1 | 4 | 8 = flat tiles in groups of that many units (the plain
+// and the residual 32 -> 32 layer on 28-column maps, at least FLAT_MIN_COLUMNS columns; the 64 -> 64 layer on 14-column maps, at least
+// FLAT_HALF_MIN_COLUMNS columns whose slabs all fit, s16_flat_half_fits; offsets of four units inside 32 bits); -4: flat tiles were asked for
+// (dil bit 0x2000) where the form does not exist.  dil bit 0x1000 keeps the row form.
 extern "C" int drc_conv3d_k3_s16_flat(const drc_s16conv_params* pp) {
     if (!pp) return -1;
     const drc_s16conv_params& p = *pp;
     const bool forced = p.dil & 0x2000;
     const long unit16 = (long)(p.D + 2) * (p.H + 2) * (p.W + 2) * 128;
-    const bool can = p.cin == 32 && p.cout == 32 && p.W == 28 && p.D > 0 && p.H > 0 && p.N > 0 && p.x && p.y16 && !p.y32 && !p.head && !p.left && !p.right &&
-                     4 * unit16 < 0x7FFFFF00L;
+    const bool half = p.cin == 64 && p.cout == 64 && p.W == 14;
+    const bool shape = (p.cin == 32 && p.cout == 32 && p.W == 28) || half;
+    const bool can = shape && p.D > 0 && p.H > 0 && p.N > 0 && p.x && p.y16 && !p.y32 && !p.head && !p.left && !p.right &&
+                     4 * (p.cout / 32) * unit16 < 0x7FFFFF00L && (!half || s16_flat_half_fits(p.N, s16_flat_group(p), p.H));
     if (p.dil & 0x1000) return forced ? -1 : 0;
     if (!can) return forced ? -4 : 0;
-    if (!forced && s16_flat_columns(p) < FLAT_MIN_COLUMNS) return 0;
-    return (p.dil & 0x4000) ? 1 : 4;
+    if (!forced && s16_flat_columns(p) < (half ? FLAT_HALF_MIN_COLUMNS : FLAT_MIN_COLUMNS)) return 0;
+    return (int)s16_flat_group(p);
 }
 
 extern "C" int drc_conv3d_k3_s16_fwd(const drc_s16conv_params* pp, void* stream) {
@@ -781,7 +825,12 @@ extern "C" int drc_conv3d_k3_s16_fwd(const drc_s16conv_params* pp, void* stream)
     if (cv) return launch<4, true>(p, s);
     const int flat = drc_conv3d_k3_s16_flat(pp);
     if (flat < 0) return flat;
-    if (flat) return p.res ? launch2<2, false, 0, 28, true, false>(p, s) : launch2<2, false, 0, 28, false, false>(p, s);
+    if (flat) {
+        drc_s16conv_params q = p;                   // the kernel reads the group size from the bits alone
+        q.dil = (p.dil & ~0x1C000) | (flat == 1 ? 0x4000 : flat == 8 ? 0x8000 : 0x10000);
+        if (p.cin == 64) return p.res ? launch2<4, false, 0, 14, true, false>(q, s) : launch2<4, false, 0, 14, false, false>(q, s);
+        return p.res ? launch2<2, false, 0, 28, true, false>(q, s) : launch2<2, false, 0, 28, false, false>(q, s);
+    }
     if (p.W <= 7) return p.cin == 32 ? launch<2, false, 4, 7>(p, s) : launch<4, false, 4, 7>(p, s);
     if (p.W <= 14) return p.cin == 32 ? launch<2, false, 2, 14>(p, s) : launch<4, false, 2, 14>(p, s);
     return p.cin == 32 ? launch<2, false>(p, s) : launch<4, false>(p, s);

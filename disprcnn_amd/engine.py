@@ -1389,6 +1389,7 @@ LASTCONV_S16 = {"enabled": True}     # eval, split-f16 2D schedule: lastconv[0] 
 S16 = {"enabled": True}       # eval: the stride-1 3x3x3 layers at full resolution on the f16 matrix cores in split arithmetic (convs16.hip)
 HEAD_ROWS = {"enabled": True}        # eval, fused heads on 28-column maps: the head launches sum the width taps (rows layout, 16 B per voxel) and ONE gather adds the three heads into cost3; False: the 12-float slots + a gather per head (A/B switch, read at every forward)
 FLAT_TILES = {"enabled": True, "group": 4}   # the plain / residual 32 -> 32 layers on 28-column maps: MFMA tiles of 32 consecutive voxels of a group of `group` (4 or 1) units instead of one 28-voxel row (convs16.hip; the library keeps small launches on rows); False: row tiles; "force": True asks for flat tiles whatever the launch's size (A/B switch, read at every run())
+FLAT_TILES_HALF = {"enabled": True, "group": 8}   # the same switch for the hourglass' half-resolution 64 -> 64 layers on 14-column maps (conv2 of each hourglass): tiles of 32 consecutive voxels of a group of `group` (8, 4 or 1) units instead of 2 x 14; "force" as above (read at every run())
 CV_WIDE = {"enabled": True}   # eval, large batches: the cost-volume layer with two rows per work item (convs16w.hip); False: convs16.hip's one-row form (A/B switch, read at every run())
 
 
@@ -1648,9 +1649,14 @@ class ConvPlanS16:
         return self.kind == "s1" and self._wide_ok and bool(CV_WIDE["enabled"])
 
     def _flat_bits(self):
-        """FLAT_TILES as the library's `dil` bits of drc_conv3d_k3_s16_fwd: 0x1000 row tiles, 0x2000 flat tiles forced, 0x4000 groups of one unit."""
+        """FLAT_TILES as the library's `dil` bits of drc_conv3d_k3_s16_fwd: 0x1000 row tiles, 0x2000 flat tiles forced, 0x4000 groups of one unit
+        (FLAT_TILES_HALF for the 64 -> 64 layers on 14-column maps: also 0x8000 groups of eight, 0x10000 of four)."""
         if self.kind != "s1" or self.cv:
             return 0
+        if (self.cin, self.cout, self.W) == (64, 64, 14):        # the half-resolution form has a switch and group sizes of its own
+            if not FLAT_TILES_HALF["enabled"]:
+                return 0x1000
+            return (0x2000 if FLAT_TILES_HALF.get("force") else 0) | {1: 0x4000, 8: 0x8000, 4: 0x10000}[int(FLAT_TILES_HALF["group"])]
         if not FLAT_TILES["enabled"]:
             return 0x1000
         return (0x2000 if FLAT_TILES.get("force") else 0) | (0x4000 if int(FLAT_TILES["group"]) == 1 else 0)

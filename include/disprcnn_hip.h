@@ -366,7 +366,9 @@ typedef struct drc_s16conv_params {
     int32_t lo4;         /* cost-volume variant: disparity of volume slice 0 (mindisp/4) */
     int32_t dil;         /* drc_conv2d_k3_s16_fwd only: dilation (0 or 1: none; 2).  drc_conv3d_k3_s16_fwd reads its high bits as switches: 0x800 keeps
                             the one-row cost-volume kernel; 0x1000 keeps row tiles, 0x2000 asks for flat tiles (-4 where that form does not exist),
-                            0x4000: flat tiles in groups of one unit instead of four (drc_conv3d_k3_s16_flat below) */
+                            0x4000: flat tiles in groups of one unit instead of four; the 64 -> 64 form on 14-column maps also 0x8000: groups of
+                            eight, 0x10000: of four (none of the three: the library's default, eight).  Bits from 0x20000 up are free
+                            (drc_conv3d_k3_s16_flat below) */
     float* head;         /* drc_conv3d_k3_s16_fwd, cin = cout = 32, W % 28 == 0, D >= 6, y16 = y32 = res = NULL: the layer is classif[0] of a head and
                             its output is not stored; the in-plane partial sums of the 32 -> 1 convolution behind it (classif[2],
                             stackhourglass.py:78-88) are: float [N][D][H][W][12], S[kh*3+kw] of the SOURCE voxel summed over the depth taps
@@ -394,7 +396,12 @@ int drc_conv3d_k3_s16_wide(const drc_s16conv_params* p);
  * row: 24.5 instead of 28 tiles per 28 x 28 plane, the same sums in the same order -- bit-identical to the row tiles, halo and guard word
  * included.  drc_conv3d_k3_s16_flat (host code, no launch) says which form drc_conv3d_k3_s16_fwd gives a parameter block: 0 = row tiles,
  * 1 | 4 = flat tiles in groups of that many units (chosen from 2048 flat columns of 64 voxels on, smaller launches keep the row tiles; needs
- * four units' bytes below 2^31), < 0: flat tiles forced (dil bit 0x2000) on a block that has no such form. */
+ * four units' bytes below 2^31), < 0: flat tiles forced (dil bit 0x2000) on a block that has no such form.
+ * The same form for the 64 -> 64 layer on 14-column maps (round 13; cin = cout = 64, W == 14: conv2 of the hourglasses, 2 x 14 row tiles): all
+ * four waves split K, so a column is ONE tile of 32 consecutive voxels of a group of eight units (or four, or one): 49 instead of 56 columns per
+ * eight 14 x 14 planes, bit-identical to the row tiles.  Chosen from 1176 columns of 32 voxels on (192 Config-A ROIs); the library walks the
+ * columns of the launch on the host and refuses the form (0, or -4 when forced) if a column's slab would need more than 8 stacked rows or reach
+ * more than 3 units behind its first one.  Return values 1 | 4 | 8 = the group size. */
 int drc_conv3d_k3_s16_flat(const drc_s16conv_params* p);
 int drc_conv3d_k3_s16_wide_fwd(const drc_s16conv_params* p, void* stream);
 /* The second half of a fused head (p->head above): cost[n][z][y][x] = (res ? res[..] : 0) + scale * sum_{kh,kw} S[n][z][y+kh-1][x+kw-1][kh*3+kw]
