@@ -122,41 +122,33 @@ class WorkspacePool:
 
     def __init__(self, cap, device):
         self.cap, self.device = int(cap), device
-        self.full = {}          # name -> Blocked sized for cap units
+        self.full = {}          # name -> Blocked / Blocked16 / RS16 sized for cap units
+        self.geom = {}          # name -> (class, per-unit geometry) it was first requested with
         self.flat = {}          # name -> dense [cap, ...] tensor
         self.gen = 0
 
-    def blocked(self, name, N, C_, D, H, W, pd, ph, pw):
+    def _tensor(self, cls, name, N, geom):
+        """The first N units of the pool's tensor `name` (class cls, per-unit geometry geom = cls's arguments between N and device)."""
         if N > self.cap:
             raise ValueError("WorkspacePool: more units than the pool was sized for")
         full = self.full.get(name)
         if full is None:
-            full = self.full[name] = Blocked(self.cap, C_, D, H, W, pd, ph, pw, self.device)
-        elif (full.C, full.D, full.H, full.W, full.pd, full.ph, full.pw) != (C_, D, H, W, pd, ph, pw):
+            full = self.full[name] = cls(self.cap, *geom, self.device)
+            self.geom[name] = (cls, geom)
+        elif self.geom[name] != (cls, geom):
             raise ValueError(f"WorkspacePool: tensor {name!r} requested with another geometry")
-        return Blocked(N, C_, D, H, W, pd, ph, pw, self.device, storage=full.storage)
+        return cls(N, *geom, self.device, storage=full.storage)
+
+    def blocked(self, name, N, C_, D, H, W, pd, ph, pw):
+        return self._tensor(Blocked, name, N, (C_, D, H, W, pd, ph, pw))
 
     def blocked16(self, name, N, C_, D, H, W, pd, ph, pw):
         """fp16-storage tensor (Blocked16) of the pool."""
-        if N > self.cap:
-            raise ValueError("WorkspacePool: more units than the pool was sized for")
-        full = self.full.get(name)
-        if full is None:
-            full = self.full[name] = Blocked16(self.cap, C_, D, H, W, pd, ph, pw, self.device)
-        elif not isinstance(full, Blocked16) or (full.C, full.D, full.H, full.W, full.pd, full.ph, full.pw) != (C_, D, H, W, pd, ph, pw):
-            raise ValueError(f"WorkspacePool: tensor {name!r} requested with another geometry")
-        return Blocked16(N, C_, D, H, W, pd, ph, pw, self.device, storage=full.storage)
+        return self._tensor(Blocked16, name, N, (C_, D, H, W, pd, ph, pw))
 
     def rs16(self, name, N, C_, D, H, W, pd=1):
         """split-f16 tensor (RS16) of the pool."""
-        if N > self.cap:
-            raise ValueError("WorkspacePool: more units than the pool was sized for")
-        full = self.full.get(name)
-        if full is None:
-            full = self.full[name] = RS16(self.cap, C_, D, H, W, pd, self.device)
-        elif not isinstance(full, RS16) or (full.C, full.D, full.H, full.W, full.pd) != (C_, D, H, W, pd):
-            raise ValueError(f"WorkspacePool: tensor {name!r} requested with another geometry")
-        return RS16(N, C_, D, H, W, pd, self.device, storage=full.storage)
+        return self._tensor(RS16, name, N, (C_, D, H, W, pd))
 
     def dense(self, name, N, *shape):
         full = self.flat.get(name)

@@ -5,6 +5,7 @@ Graph restated from the reference (stackhourglass.py:106-174, submodule.py:106-1
 schedule of launches over blocked, zero-haloed tensors.  Workspaces and launch plans are cached
 per input shape; halos are zeroed once at allocation and never written again.
 """
+import functools
 import operator
 import weakref
 from collections import OrderedDict
@@ -12,7 +13,12 @@ from collections import OrderedDict
 import torch
 
 from ... import engine as E
+from .schedule import CONCAT, REGRESSOR_HEADS, REGRESSOR_SITES, REGRESSOR_TENSORS, STRIDE, concat_slots, trunk_sites
 from .submodule import SPP_BRANCHES, TRUNK_STAGES
+
+TRUNK = trunk_sites()
+_HEAD_OF = {h.site.plan: h for h in REGRESSOR_HEADS}
+_LAYER_KINDS = tuple(dict.fromkeys((s.kind, s.cin, s.cout, s.level) for s in REGRESSOR_SITES))     # the distinct 3x3x3 layers (_s16_layers)
 
 GRAPH_MAX_UNITS = 96     # eval: batches up to this many ROI pairs replay a captured HIP graph (PSMNet.graph_eval = "auto")
 GRAPH_MAX_ENTRIES = 16   # captured graphs kept per runtime (one per unit-count bucket and input geometry), least recently used dropped
@@ -137,6 +143,189 @@ class _LazyTensors(dict):
 
     def get(self, name, default=None):
         return self[name] if (name in self or name in self.lazy) else default
+
+
+# ------------------------------------------------------------------ the regressor's three storages
+# ONE workspace builder (PSMNetRuntime._ws3d) and ONE launch schedule (_regress) walk schedule.REGRESSOR_SITES for all three.  What differs
+# is here: how a tensor is allocated (inputs / alloc / head_tensors), how a site is planned (plan), what a launch is handed (entry: made
+# once per workspace) and how it is launched (runner), how dres0[0] gets the cost volume (first) and how the 32 -> 1 heads are finished (heads).
+class _Blocked32:
+    """fp32 Blocked tensors, eval and training: every site goes through PSMNetRuntime._site (BatchNorm, tape)."""
+    tag, costk_last = "3d", True
+
+    @staticmethod
+    def inputs(rt, ws, N, full):
+        # the 64-channel volume is the largest tensor of the stage and the fused eval path (wino3d_cv_kernel) never touches it: it is
+        # allocated (and zero-filled) on first use -- training, the non-fused path -- and planned from its geometry alone (ADVICE r2)
+        pool = ws["pool"]
+        ws["t"].lazy["cost"] = lambda: pool.blocked("cost", N, 64, *full, 1, 1, 1)
+
+    @staticmethod
+    def alloc(pool, name, N, c, dims):
+        return pool.blocked(name, N, c, *dims, 1, 1, 1)
+
+    @staticmethod
+    def head_tensors(ws, N, full):
+        pass
+
+    @staticmethod
+    def plan(rt, ws, s, N, dims):
+        t = ws["t"]
+        x = E.Blocked.geometry(N, s.cin, *dims, 1, 1, 1, rt.device) if s.costvol else t[s.x]
+        ws["p"][s.plan] = (E.plan_deconv3d(x, t[s.y], s.cout, s.relu) if s.kind == "up" else
+                           E.plan_conv3d(x, t[s.y], STRIDE[s.kind], s.cout, s.relu))
+
+    @staticmethod
+    def entry(ws, s):
+        return (s.plan, s.wname, s.x, s.y, s.res)           # the arguments of _site (and of the tape)
+
+    @staticmethod
+    def runner(rt, ws, W):
+        return functools.partial(rt._site, ws, W)
+
+    @staticmethod
+    def first(ws, W, run, cv):
+        """cv = (left, right, lo4): dres0[0] reads the blocked feature maps instead of a materialised volume (:115-130)."""
+        if cv is not None:
+            c, pl = W["dres0.0"], ws["p"]["dres0.0"]
+            pl.run_costvol(cv[0], cv[1], cv[2], c.w16_for(pl), c.scale, c.shift, ws["t"]["d0a"])
+        else:
+            run(*ws["first"])
+
+    @staticmethod
+    def heads(rt, ws, W, run):
+        t, prev = ws["t"], None
+        for e, h in ws["heads"]:
+            run(*e)
+            E.conv3d_cout1(t[h.cls_t], W[h.weight], prev, t[h.costk])          # cumulative heads
+            prev = t[h.costk]
+        return t["costk1"], t["costk2"], t["costk3"]
+
+
+class _Blocked16(_Blocked32):
+    """fp16-storage Blocked16 tensors (BASELINE configs[3]; eval only: BatchNorm folded into the fp32 epilogue)."""
+    tag, costk_last = "3d16", False
+
+    @staticmethod
+    def inputs(rt, ws, N, full):
+        if E.COSTVOL16_FUSED["enabled"]:    # left | right features, one slice: dres0[0] builds the volume's rows from it (conv16x.hip)
+            ws["t"]["pair"] = ws["pool"].blocked16("pair", N, 64, 1, *full[1:], 1, 1, 1)
+        else:
+            ws["t"]["cost"] = ws["pool"].blocked16("cost", N, 64, *full, 1, 1, 1)
+
+    @staticmethod
+    def alloc(pool, name, N, c, dims):
+        return pool.blocked16(name, N, c, *dims, 1, 1, 1)
+
+    @staticmethod
+    def plan(rt, ws, s, N, dims):
+        t, p = ws["t"], ws["p"]
+        if s.costvol and "pair" in t:
+            p[s.plan] = E.plan_conv3d16_costvol(t["pair"], t[s.y], 0, s.cout, s.relu)        # (first disparity: set per call, _costvol16)
+        elif s.kind == "up":
+            p[s.plan] = E.plan_deconv3d16(t[s.x], t[s.y], s.cout, s.relu)
+        else:
+            p[s.plan] = E.plan_conv3d16(t[s.x], t[s.y], STRIDE[s.kind], s.cout, s.relu)
+        if s.plan in _HEAD_OF:                                                              # the 32 -> 1 head is a plan of this storage
+            p[_HEAD_OF[s.plan].weight] = E.plan_conv3d16_cout1(t[s.y])
+
+    @staticmethod
+    def entry(ws, s):
+        t = ws["t"]
+        return (ws["p"][s.plan], s.wname, t["pair" if s.costvol and "pair" in t else s.x], t[s.y], t[s.res] if s.res else None)
+
+    @staticmethod
+    def runner(rt, ws, W):
+        W16 = rt._weights16(W)
+
+        def run(pl, wname, x, y, res):
+            c = W[wname]
+            pl.run(x, W16[wname], c.scale, c.shift, y, res)
+        return run
+
+    @staticmethod
+    def first(ws, W, run, cv):
+        run(*ws["first"])                       # (the volume, or the pair and its first disparity, were set by _costvol16)
+
+    @staticmethod
+    def heads(rt, ws, W, run):
+        t, p, W16, prev = ws["t"], ws["p"], rt._weights16(W), None
+        for e, h in ws["heads"]:
+            run(*e)
+            p[h.weight].run(t[h.cls_t], W16[h.weight], None, None, t[h.costk], prev)
+            prev = t[h.costk]
+        return t["costk1"], t["costk2"], t["costk3"]
+
+
+class _SplitF16(_Blocked32):
+    """RS16 tensors, every layer but the cout-1 heads in split-f16 arithmetic (round 5; eval only); ws['t']['featL'/'featR'] hold the
+    feature maps (RS16 2D).  Reference: stackhourglass.py:115-144."""
+    tag, costk_last = "3ds16", False
+
+    @staticmethod
+    def inputs(rt, ws, N, full):
+        for name in ("featL", "featR"):
+            ws["t"][name] = ws["pool"].rs16(name, N, 32, 1, *full[1:], 0)
+
+    @staticmethod
+    def alloc(pool, name, N, c, dims):
+        return None if name.startswith("cls_t") else pool.rs16(name, N, c, *dims, 1)   # (cls_t: head_tensors)
+
+    @staticmethod
+    def head_tensors(ws, N, full):
+        # the heads: classif[0] + the 32 -> 1 layer fused (convs16.hip HEAD form: partial sums S, 48 B per voxel, one buffer for the three
+        # heads) where the map is a multiple of 28 columns; else classif[0] writes a blocked fp32 tensor that cout1_mfma.hip reads
+        t, pool = ws["t"], ws["pool"]
+        ws["fused_heads"] = E.HEAD_FUSED["enabled"] and full[2] % 28 == 0 and full[0] >= 6 and full[0] % 3 == 0
+        if ws["fused_heads"]:
+            t["hs"] = pool.dense("hs", N, *full, 12)
+        else:
+            for h in REGRESSOR_HEADS:
+                t[h.cls_t] = pool.blocked(h.cls_t, N, 32, *full, 1, 1, 1)    # fp32: the cout-1 head reads it
+
+    @staticmethod
+    def plan(rt, ws, s, N, dims):
+        ws["p"][s.plan] = E.ConvPlanS16(N, s.cin, s.cout, *dims, s.relu, cv=s.costvol, device=rt.device, kind=s.kind)
+
+    @staticmethod
+    def entry(ws, s):
+        t = ws["t"]                             # (x16, y16, res; dres0[0] reads featL / featR, a head writes hs or its fp32 cls_t)
+        return (ws["p"][s.plan], s.wname, None if s.costvol else t[s.x], None if s.plan in _HEAD_OF else t[s.y], t[s.res] if s.res else None)
+
+    @staticmethod
+    def runner(rt, ws, W):
+        def run(pl, wname, x, y16, res, **kw):
+            c = W[wname]
+            w16, sc16 = c.s16()
+            pl.run(x, w16, sc16, c.shift, y16=y16, res=res, **kw)
+        return run
+
+    @staticmethod
+    def first(ws, W, run, cv):
+        """cv = lo4, the first disparity / 4."""
+        run(*ws["first"], left=ws["t"]["featL"], right=ws["t"]["featR"], lo4=cv)
+
+    @staticmethod
+    def heads(rt, ws, W, run):
+        t, prev = ws["t"], None
+        h16 = rt._head_weights_s16() if ws["fused_heads"] else None
+        if h16 is not None and E.HEAD_ROWS["enabled"] and t["costk3"].shape[-1] == 28:
+            # one x tile per row: the head launches sum the width taps themselves (rows layout, 16 B per voxel: the S buffer holds all three
+            # heads) and ONE gather adds the three heads into cost3 -- cost1 / cost2 are the training path's and are not produced here
+            rows = t["hs"].view(3, -1)
+            for e, h in ws["heads"]:
+                run(*e, head=(h16[h.k][0], rows[h.k - 1]), head_rows=True)
+            E.head_gather_rows([rows[0], rows[1], rows[2]], [h16[k][1] for k in (1, 2, 3)], None, t["costk3"])
+            return None, None, t["costk3"]
+        for e, h in ws["heads"]:
+            if h16 is not None:
+                run(*e, head=(h16[h.k][0], t["hs"]))
+                E.head_gather(t["hs"], h16[h.k][1], prev, t[h.costk])                         # cumulative heads
+            else:
+                run(*e, y32=t[h.cls_t])
+                E.conv3d_cout1(t[h.cls_t], W[h.weight], prev, t[h.costk])
+            prev = t[h.costk]
+        return t["costk1"], t["costk2"], t["costk3"]
 
 
 class PSMNetRuntime:
@@ -293,24 +482,13 @@ class PSMNetRuntime:
         def cb3(name, seq, transposed=False):
             W[name] = _Conv(seq[0], seq[1], dev, transposed)
 
-        cb3("dres0.0", m.dres0[0]); cb3("dres0.2", m.dres0[2])
-        cb3("dres1.0", m.dres1[0]); cb3("dres1.2", m.dres1[2])
-        for hg in ("dres2", "dres3", "dres4"):
-            h = getattr(m, hg)
-            cb3(hg + ".conv1", h.conv1[0]); cb3(hg + ".conv2", h.conv2); cb3(hg + ".conv3", h.conv3[0])
-            cb3(hg + ".conv4", h.conv4[0]); cb3(hg + ".conv5", h.conv5, True); cb3(hg + ".conv6", h.conv6, True)
-        for c in ("classif1", "classif2", "classif3"):
-            seq = getattr(m, c)
-            cb3(c + ".0", seq[0])
-            W[c + ".2"] = E.pack_weight_cout1(seq[2].weight.detach().to(device=dev, dtype=torch.float32))
+        for s in REGRESSOR_SITES:
+            cb3(s.wname, m.get_submodule(s.prefix), s.kind == "up")
+        for h in REGRESSOR_HEADS:
+            W[h.weight] = E.pack_weight_cout1(m.get_submodule(h.weight).weight.detach().to(device=dev, dtype=torch.float32))
         fe = m.feature_extraction
-        for i in (0, 2, 4):
-            cb3(f"fe.firstconv.{i}", fe.firstconv[i])
-        for name, planes, nblk, stride, dil in TRUNK_STAGES:
-            for b, unit in enumerate(getattr(fe, name)):
-                cb3(f"fe.{name}.{b}.conv1", unit.conv1[0]); cb3(f"fe.{name}.{b}.conv2", unit.conv2)
-                if unit.downsample is not None:
-                    cb3(f"fe.{name}.{b}.down", unit.downsample)
+        for s in TRUNK.stem + TRUNK.blocks:
+            cb3(s.wname, fe.get_submodule(s.prefix))
         for name, _ in SPP_BRANCHES:
             cb3(f"fe.{name}", getattr(fe, name)[1])
         cb3("fe.lastconv.0", fe.lastconv[0])
@@ -367,48 +545,43 @@ class PSMNetRuntime:
             self._tape.append(("site", ws, plan, wname, x, y, res))
 
     # ------------------------------------------------------------------ 3D regressor
-    def _ws3d(self, N, Dp, Hp, Wp):
-        key = self._slotted(("3d", N, Dp, Hp, Wp))
+    def _ws3d(self, ad, N, Dp, Hp, Wp):
+        """The regressor's workspace in the storage of adapter `ad`: tensors, plans and the prepared launches of _regress."""
+        key = self._slotted((ad.tag, N, Dp, Hp, Wp))
         ws = self._ws_get(key)
         if ws is not None:
             return ws
-        pool = self._pool_for(self._slotted(("3d", Dp, Hp, Wp)), N)
+        pool = self._pool_for(self._slotted((ad.tag, Dp, Hp, Wp)), N)
         full = (Dp, Hp, Wp)
         half = tuple(-(-s // 2) for s in full)
         quart = tuple(-(-s // 2) for s in half)
         if tuple(2 * s for s in half) != full or tuple(2 * s for s in quart) != half:
             raise ValueError(f"cost-volume dims {full} must be divisible by 4 (D,H,W multiples of 16; SURVEY 8)")
-        t = _LazyTensors()
+        dims = (full, half, quart)
+        t, p = _LazyTensors(), {}
+        ws = dict(t=t, p=p, pool=pool, ad=ad)
+        pending = iter(REGRESSOR_HEADS)          # costk1..3: with their hourglass or after the last one -- each storage keeps the order it had
 
-        def B(name, c, d, h, w):
-            t[name] = pool.blocked(name, N, c, d, h, w, 1, 1, 1)
+        def costk(h):
+            t[h.costk] = pool.dense(h.costk, N, *full)
 
-        # the 64-channel volume is the largest tensor of the stage and the fused eval path (wino3d_cv_kernel) never touches it: it is
-        # allocated (and zero-filled) on first use -- training, the non-fused path -- and planned from its geometry alone
-        t.lazy["cost"] = lambda: pool.blocked("cost", N, 64, *full, 1, 1, 1)
-        cost_geom = E.Blocked.geometry(N, 64, *full, 1, 1, 1, self.device)
-        for n in ("d0a", "cost0a", "d1a", "cost0", "out1", "out2", "out3", "cls_t1", "cls_t2", "cls_t3"):
-            B(n, 32, *full)
-        for k in (1, 2, 3):
-            B(f"hg{k}.c1", 64, *half); B(f"hg{k}.pre", 64, *half); B(f"hg{k}.post", 64, *half)
-            B(f"hg{k}.c3", 64, *quart); B(f"hg{k}.c4", 64, *quart)
-        for k in (1, 2, 3):
-            t[f"costk{k}"] = pool.dense(f"costk{k}", N, *full)
-        p = {}
-        p["dres0.0"] = E.plan_conv3d(cost_geom, t["d0a"], 1, 32, True)
-        p["dres0.2"] = E.plan_conv3d(t["d0a"], t["cost0a"], 1, 32, True)
-        p["dres1.0"] = E.plan_conv3d(t["cost0a"], t["d1a"], 1, 32, True)
-        p["dres1.2"] = E.plan_conv3d(t["d1a"], t["cost0"], 1, 32, False)
-        for k in (1, 2, 3):
-            src = t["cost0"] if k == 1 else t[f"out{k - 1}"]
-            p[f"hg{k}.conv1"] = E.plan_conv3d(src, t[f"hg{k}.c1"], 2, 64, True)
-            p[f"hg{k}.conv2"] = E.plan_conv3d(t[f"hg{k}.c1"], t[f"hg{k}.pre"], 1, 64, True)
-            p[f"hg{k}.conv3"] = E.plan_conv3d(t[f"hg{k}.pre"], t[f"hg{k}.c3"], 2, 64, True)
-            p[f"hg{k}.conv4"] = E.plan_conv3d(t[f"hg{k}.c3"], t[f"hg{k}.c4"], 1, 64, True)
-            p[f"hg{k}.conv5"] = E.plan_deconv3d(t[f"hg{k}.c4"], t[f"hg{k}.post"], 64, True)
-            p[f"hg{k}.conv6"] = E.plan_deconv3d(t[f"hg{k}.post"], t[f"out{k}"], 32, False)
-            p[f"classif{k}.0"] = E.plan_conv3d(t[f"out{k}"], t[f"cls_t{k}"], 1, 32, True)
-        ws = dict(t=t, p=p, pool=pool, flops=sum(pl.flops for pl in p.values()) + 3 * 2 * 27 * 32 * N * Dp * Hp * Wp)
+        ad.inputs(self, ws, N, full)
+        for name, c, lvl in REGRESSOR_TENSORS:
+            v = ad.alloc(pool, name, N, c, dims[lvl])
+            if v is not None:
+                t[name] = v
+            if not ad.costk_last and name.endswith(".c4"):
+                costk(next(pending))
+        for h in pending:
+            costk(h)
+        ad.head_tensors(ws, N, full)
+        for s in REGRESSOR_SITES:
+            ad.plan(self, ws, s, N, dims[s.level])
+        # what _regress iterates: dres0[0], the other layers in launch order, and the heads (classif{k}[0] is launched with its head)
+        body = [ad.entry(ws, s) for s in REGRESSOR_SITES if s.plan not in _HEAD_OF]
+        ws.update(first=body[0], body=body[1:], heads=[(ad.entry(ws, h.site), h) for h in REGRESSOR_HEADS])
+        # (+ the 32 -> 1 heads where they are no plans of their own)
+        ws["flops"] = sum(pl.flops for pl in p.values()) + (0 if REGRESSOR_HEADS[0].weight in p else 3 * 2 * 27 * 32 * N * Dp * Hp * Wp)
         return self._ws_put(key, ws)
 
     def _fuse_costvol(self, ws, training):
@@ -416,52 +589,26 @@ class PSMNetRuntime:
         return bool(not training and self._tape is None and E.WINO["fuse_costvol"] and ws["p"]["dres0.0"].wino)
 
     def _regress(self, ws, W, cv=None):
-        """dres0..dres4 + classif heads on ws['t']['cost'] -> dense cost3 [N,D',H',W'] (reference :130-144).
-        cv = (left, right, lo4): dres0[0] reads the blocked feature maps instead of a materialised volume (:115-130)."""
-        t, p = ws["t"], ws["p"]
-
-        def run(plan, wname, x, y, res=None):
-            self._site(ws, W, plan, wname, x, y, res)
-
-        if cv is not None:
-            c, pl = W["dres0.0"], p["dres0.0"]
-            pl.run_costvol(cv[0], cv[1], cv[2], c.w16_for(pl), c.scale, c.shift, t["d0a"])
-        else:
-            run("dres0.0", "dres0.0", "cost", "d0a")
-        run("dres0.2", "dres0.2", "d0a", "cost0a")
-        run("dres1.0", "dres1.0", "cost0a", "d1a")
-        run("dres1.2", "dres1.2", "d1a", "cost0", res="cost0a")           # dres1(cost0)+cost0, no relu
-        for k, hg in ((1, "dres2"), (2, "dres3"), (3, "dres4")):
-            src = "cost0" if k == 1 else f"out{k - 1}"
-            postsqu = None if k == 1 else f"hg{k - 1}.post"                 # dres3(.., post1), dres4(.., post2)
-            presqu = f"hg{k}.pre" if k == 1 else "hg1.pre"                  # pre1 reused by dres3 AND dres4 (:136,:139)
-            run(f"hg{k}.conv1", hg + ".conv1", src, f"hg{k}.c1")
-            run(f"hg{k}.conv2", hg + ".conv2", f"hg{k}.c1", f"hg{k}.pre", res=postsqu)   # relu(conv2 + postsqu)
-            run(f"hg{k}.conv3", hg + ".conv3", f"hg{k}.pre", f"hg{k}.c3")
-            run(f"hg{k}.conv4", hg + ".conv4", f"hg{k}.c3", f"hg{k}.c4")
-            run(f"hg{k}.conv5", hg + ".conv5", f"hg{k}.c4", f"hg{k}.post", res=presqu)   # relu(conv5 + presqu|pre)
-            run(f"hg{k}.conv6", hg + ".conv6", f"hg{k}.post", f"out{k}", res="cost0")    # out_k = conv6 + cost0
-        prev = None
-        for k in (1, 2, 3):
-            run(f"classif{k}.0", f"classif{k}.0", f"out{k}", f"cls_t{k}")
-            E.conv3d_cout1(t[f"cls_t{k}"], W[f"classif{k}.2"], prev, t[f"costk{k}"])          # cumulative heads
-            prev = t[f"costk{k}"]
-        return t["costk1"], t["costk2"], t["costk3"]
+        """dres0..dres4 + classif heads -> dense (cost1, cost2, cost3) [N,D',H',W'] (reference :130-144) in the storage the workspace was
+        built for; cv: what that storage's dres0[0] needs besides its tensors (see the adapters' `first`)."""
+        ad = ws["ad"]
+        run = ad.runner(self, ws, W)
+        ad.first(ws, W, run, cv)
+        for e in ws["body"]:
+            run(*e)
+        return ad.heads(self, ws, W, run)
 
     # ------------------------------------------------------------------ split-f16 regressor (round 5; eval only)
     @staticmethod
     def _s16_layers(Dp, Hp, Wp):
-        """(kind, cin, cout, input dims) of every 3x3x3 layer of the regressor but the three cout-1 heads."""
-        full = (Dp, Hp, Wp)
-        half = tuple(s // 2 for s in full)
-        quart = tuple(s // 2 for s in half)
-        return [("s1", 64, 32, full), ("s1", 32, 32, full), ("s2", 32, 64, full), ("s1", 64, 64, half), ("s2", 64, 64, half),
-                ("s1", 64, 64, quart), ("up", 64, 64, quart), ("up", 64, 32, half)]
+        """(kind, cin, cout, input dims) of every distinct 3x3x3 layer of the regressor but the three cout-1 heads (read on every forward)."""
+        dims = ((Dp, Hp, Wp), (Dp // 2, Hp // 2, Wp // 2), (Dp // 4, Hp // 4, Wp // 4))
+        return [(kind, cin, cout, dims[level]) for kind, cin, cout, level in _LAYER_KINDS]
 
     def _use_s16(self, training, Dp, Hp, Wp):
         """Eval: every 3x3x3 layer of the regressor runs in split-f16 arithmetic on the f16 matrix cores (convs16*.hip: fp32-class results,
         DESIGN 3.7) when the volume's shape is one the kernels take -- the three cout-1 heads fused into the layer in front of them where the
-        map is a multiple of 28 columns (_ws3d_s16), else on cout1_mfma.hip; PSMNet.regressor_math = "f32" keeps the fp32 MFMA kernels of
+        map is a multiple of 28 columns (_SplitF16.head_tensors), else on cout1_mfma.hip; PSMNet.regressor_math = "f32" keeps the fp32 MFMA kernels of
         rounds 1-4."""
         mode = getattr(self.model, "regressor_math", "auto")
         if mode not in ("auto", "f32", "f16x2"):
@@ -483,53 +630,6 @@ class PSMNetRuntime:
             self._s16_used = True
         return use
 
-    def _ws3d_s16(self, N, Dp, Hp, Wp):
-        key = self._slotted(("3ds16", N, Dp, Hp, Wp))
-        ws = self._ws_get(key)
-        if ws is not None:
-            return ws
-        pool = self._pool_for(self._slotted(("3ds16", Dp, Hp, Wp)), N)
-        full = (Dp, Hp, Wp)
-        half = tuple(s // 2 for s in full)
-        quart = tuple(s // 2 for s in half)
-        t = {}
-
-        def S(name, c, d, h, w, pd=1):
-            t[name] = pool.rs16(name, N, c, d, h, w, pd)
-
-        S("featL", 32, 1, Hp, Wp, 0); S("featR", 32, 1, Hp, Wp, 0)
-        for n in ("d0a", "cost0a", "d1a", "cost0", "out1", "out2", "out3"):
-            S(n, 32, *full)
-        for k in (1, 2, 3):
-            S(f"hg{k}.c1", 64, *half); S(f"hg{k}.pre", 64, *half); S(f"hg{k}.post", 64, *half)
-            S(f"hg{k}.c3", 64, *quart); S(f"hg{k}.c4", 64, *quart)
-            t[f"costk{k}"] = pool.dense(f"costk{k}", N, *full)
-        # the heads: classif[0] + the 32 -> 1 layer fused (convs16.hip HEAD form: partial sums S, 48 B per voxel, one buffer for the three
-        # heads) where the map is a multiple of 28 columns; else classif[0] writes a blocked fp32 tensor that cout1_mfma.hip reads
-        fused = E.HEAD_FUSED["enabled"] and Wp % 28 == 0 and Dp >= 6 and Dp % 3 == 0
-        if fused:
-            t["hs"] = pool.dense("hs", N, Dp, Hp, Wp, 12)
-        else:
-            for k in (1, 2, 3):
-                t[f"cls_t{k}"] = pool.blocked(f"cls_t{k}", N, 32, *full, 1, 1, 1)    # fp32: the cout-1 head reads it
-        dev = self.device
-        P = lambda kind, ci, co, dims, relu, cv=False: E.ConvPlanS16(N, ci, co, *dims, relu, cv=cv, device=dev, kind=kind)
-        p = {}
-        p["dres0.0"] = P("s1", 64, 32, full, True, cv=True)
-        p["dres0.2"] = P("s1", 32, 32, full, True)
-        p["dres1.0"] = P("s1", 32, 32, full, True)
-        p["dres1.2"] = P("s1", 32, 32, full, False)
-        for k in (1, 2, 3):
-            p[f"hg{k}.conv1"] = P("s2", 32, 64, full, True)
-            p[f"hg{k}.conv2"] = P("s1", 64, 64, half, True)
-            p[f"hg{k}.conv3"] = P("s2", 64, 64, half, True)
-            p[f"hg{k}.conv4"] = P("s1", 64, 64, quart, True)
-            p[f"hg{k}.conv5"] = P("up", 64, 64, quart, True)
-            p[f"hg{k}.conv6"] = P("up", 64, 32, half, False)
-            p[f"classif{k}.0"] = P("s1", 32, 32, full, True)
-        ws = dict(t=t, p=p, pool=pool, fused_heads=fused, flops=sum(pl.flops for pl in p.values()) + 3 * 2 * 27 * 32 * N * Dp * Hp * Wp)
-        return self._ws_put(key, ws)
-
     def _head_weights_s16(self):
         """{k: (packed 32 -> 1 weights of the fused head, 2^-wexp)} for classif1..3[2], rebuilt with the packed fp32 weights."""
         if getattr(self, "_h16_version", None) == self._weights_version and getattr(self, "_h16", None) is not None:
@@ -541,50 +641,6 @@ class PSMNetRuntime:
             out[k] = (wp.to(self.device), 2.0 ** -wexp)
         self._h16, self._h16_version = out, self._weights_version
         return out
-
-    def _regress_s16(self, ws, W, lo4):
-        """The schedule of _regress on RS16 tensors, every layer but the cout-1 heads in split-f16 arithmetic; ws['t']['featL'/'featR'] hold
-        the feature maps (RS16 2D).  Reference: stackhourglass.py:115-144."""
-        t, p = ws["t"], ws["p"]
-
-        def run(plan, wname, x, y16=None, y32=None, res=None, **kw):
-            w16, sc16 = W[wname].s16()
-            p[plan].run(t[x] if x else None, w16, sc16, W[wname].shift, y16=t[y16] if y16 else None, y32=t[y32] if y32 else None,
-                        res=t[res] if res else None, **kw)
-
-        run("dres0.0", "dres0.0", None, y16="d0a", left=t["featL"], right=t["featR"], lo4=lo4)
-        run("dres0.2", "dres0.2", "d0a", y16="cost0a")
-        run("dres1.0", "dres1.0", "cost0a", y16="d1a")
-        run("dres1.2", "dres1.2", "d1a", y16="cost0", res="cost0a")             # dres1(cost0)+cost0, no relu
-        for k, hg in ((1, "dres2"), (2, "dres3"), (3, "dres4")):
-            src = "cost0" if k == 1 else f"out{k - 1}"
-            postsqu = None if k == 1 else f"hg{k - 1}.post"                      # dres3(.., post1), dres4(.., post2)
-            presqu = f"hg{k}.pre" if k == 1 else "hg1.pre"                       # pre1 reused by dres3 AND dres4 (:136,:139)
-            run(f"hg{k}.conv1", hg + ".conv1", src, y16=f"hg{k}.c1")
-            run(f"hg{k}.conv2", hg + ".conv2", f"hg{k}.c1", y16=f"hg{k}.pre", res=postsqu)      # relu(conv2 + postsqu)
-            run(f"hg{k}.conv3", hg + ".conv3", f"hg{k}.pre", y16=f"hg{k}.c3")
-            run(f"hg{k}.conv4", hg + ".conv4", f"hg{k}.c3", y16=f"hg{k}.c4")
-            run(f"hg{k}.conv5", hg + ".conv5", f"hg{k}.c4", y16=f"hg{k}.post", res=presqu)      # relu(conv5 + presqu|pre)
-            run(f"hg{k}.conv6", hg + ".conv6", f"hg{k}.post", y16=f"out{k}", res="cost0")       # out_k = conv6 + cost0
-        prev = None
-        h16 = self._head_weights_s16() if ws["fused_heads"] else None
-        if h16 is not None and E.HEAD_ROWS["enabled"] and t["costk3"].shape[-1] == 28:
-            # one x tile per row: the head launches sum the width taps themselves (rows layout, 16 B per voxel: the S buffer holds all three
-            # heads) and ONE gather adds the three heads into cost3 -- cost1 / cost2 are the training path's and are not produced here
-            rows = t["hs"].view(3, -1)
-            for k in (1, 2, 3):
-                run(f"classif{k}.0", f"classif{k}.0", f"out{k}", head=(h16[k][0], rows[k - 1]), head_rows=True)
-            E.head_gather_rows([rows[0], rows[1], rows[2]], [h16[k][1] for k in (1, 2, 3)], None, t["costk3"])
-            return None, None, t["costk3"]
-        for k in (1, 2, 3):
-            if h16 is not None:
-                run(f"classif{k}.0", f"classif{k}.0", f"out{k}", head=(h16[k][0], t["hs"]))
-                E.head_gather(t["hs"], h16[k][1], prev, t[f"costk{k}"])                         # cumulative heads
-            else:
-                run(f"classif{k}.0", f"classif{k}.0", f"out{k}", y32=f"cls_t{k}")
-                E.conv3d_cout1(t[f"cls_t{k}"], W[f"classif{k}.2"], prev, t[f"costk{k}"])
-            prev = t[f"costk{k}"]
-        return t["costk1"], t["costk2"], t["costk3"]
 
     # ------------------------------------------------------------------ fp16-storage regressor (BASELINE configs[3]; eval only)
     def _weights16(self, W):
@@ -601,52 +657,6 @@ class PSMNetRuntime:
         self._w16, self._w16_version = out, self._weights_version
         return out
 
-    def _ws3d16(self, N, Dp, Hp, Wp):
-        key = self._slotted(("3d16", N, Dp, Hp, Wp))
-        ws = self._ws_get(key)
-        if ws is not None:
-            return ws
-        pool = self._pool_for(self._slotted(("3d16", Dp, Hp, Wp)), N)
-        full = (Dp, Hp, Wp)
-        half = tuple(-(-s // 2) for s in full)
-        quart = tuple(-(-s // 2) for s in half)
-        if tuple(2 * s for s in half) != full or tuple(2 * s for s in quart) != half:
-            raise ValueError(f"cost-volume dims {full} must be divisible by 4 (D,H,W multiples of 16; SURVEY 8)")
-        t = {}
-
-        def B(name, c, d, h, w):
-            t[name] = pool.blocked16(name, N, c, d, h, w, 1, 1, 1)
-
-        fused_cv = E.COSTVOL16_FUSED["enabled"]
-        if fused_cv:
-            B("pair", 64, 1, Hp, Wp)            # left | right features, one slice: dres0[0] builds the volume's rows from it (conv16x.hip)
-        else:
-            B("cost", 64, *full)
-        for n in ("d0a", "cost0a", "d1a", "cost0", "out1", "out2", "out3", "cls_t1", "cls_t2", "cls_t3"):
-            B(n, 32, *full)
-        for k in (1, 2, 3):
-            B(f"hg{k}.c1", 64, *half); B(f"hg{k}.pre", 64, *half); B(f"hg{k}.post", 64, *half)
-            B(f"hg{k}.c3", 64, *quart); B(f"hg{k}.c4", 64, *quart)
-            t[f"costk{k}"] = pool.dense(f"costk{k}", N, *full)
-        p = {}
-        p["dres0.0"] = (E.plan_conv3d16_costvol(t["pair"], t["d0a"], 0, 32, True) if fused_cv        # (first disparity: set per call, _costvol16)
-                        else E.plan_conv3d16(t["cost"], t["d0a"], 1, 32, True))
-        p["dres0.2"] = E.plan_conv3d16(t["d0a"], t["cost0a"], 1, 32, True)
-        p["dres1.0"] = E.plan_conv3d16(t["cost0a"], t["d1a"], 1, 32, True)
-        p["dres1.2"] = E.plan_conv3d16(t["d1a"], t["cost0"], 1, 32, False)
-        for k in (1, 2, 3):
-            src = t["cost0"] if k == 1 else t[f"out{k - 1}"]
-            p[f"hg{k}.conv1"] = E.plan_conv3d16(src, t[f"hg{k}.c1"], 2, 64, True)
-            p[f"hg{k}.conv2"] = E.plan_conv3d16(t[f"hg{k}.c1"], t[f"hg{k}.pre"], 1, 64, True)
-            p[f"hg{k}.conv3"] = E.plan_conv3d16(t[f"hg{k}.pre"], t[f"hg{k}.c3"], 2, 64, True)
-            p[f"hg{k}.conv4"] = E.plan_conv3d16(t[f"hg{k}.c3"], t[f"hg{k}.c4"], 1, 64, True)
-            p[f"hg{k}.conv5"] = E.plan_deconv3d16(t[f"hg{k}.c4"], t[f"hg{k}.post"], 64, True)
-            p[f"hg{k}.conv6"] = E.plan_deconv3d16(t[f"hg{k}.post"], t[f"out{k}"], 32, False)
-            p[f"classif{k}.0"] = E.plan_conv3d16(t[f"out{k}"], t[f"cls_t{k}"], 1, 32, True)
-            p[f"classif{k}.2"] = E.plan_conv3d16_cout1(t[f"cls_t{k}"])
-        ws = dict(t=t, p=p, pool=pool, flops=sum(pl.flops for pl in p.values()))
-        return self._ws_put(key, ws)
-
     def _costvol16(self, ws, mn, mx, left=None, right=None, in_pad=-1, feat16=None, right_first=0):
         """The fp16 cost volume of stackhourglass.py:115-128 from fp32 features (NCHW, or blocked 2D storage with halo in_pad) or from a
         Blocked16 feature tensor -- or, fused (engine.COSTVOL16_FUSED), only the one-slice feature pair dres0[0] builds the volume's rows from."""
@@ -658,36 +668,6 @@ class PSMNetRuntime:
             E.cost_volume16_from16(feat16, right_first, dst, lo, hi)
         else:
             E.cost_volume16_blocked(left, right, dst, lo, hi, in_pad)
-
-    def _regress16(self, ws, W):
-        """The schedule of _regress on fp16-storage tensors (eval: BatchNorm folded into the fp32 epilogue)."""
-        t, p = ws["t"], ws["p"]
-        W16 = self._weights16(W)
-
-        def run(plan, wname, x, y, res=None):
-            c = W[wname]
-            p[plan].run(t[x], W16[wname], c.scale, c.shift, t[y], t[res] if res else None)
-
-        run("dres0.0", "dres0.0", "pair" if "pair" in t else "cost", "d0a")
-        run("dres0.2", "dres0.2", "d0a", "cost0a")
-        run("dres1.0", "dres1.0", "cost0a", "d1a")
-        run("dres1.2", "dres1.2", "d1a", "cost0", res="cost0a")
-        for k, hg in ((1, "dres2"), (2, "dres3"), (3, "dres4")):
-            src = "cost0" if k == 1 else f"out{k - 1}"
-            postsqu = None if k == 1 else f"hg{k - 1}.post"
-            presqu = f"hg{k}.pre" if k == 1 else "hg1.pre"
-            run(f"hg{k}.conv1", hg + ".conv1", src, f"hg{k}.c1")
-            run(f"hg{k}.conv2", hg + ".conv2", f"hg{k}.c1", f"hg{k}.pre", res=postsqu)
-            run(f"hg{k}.conv3", hg + ".conv3", f"hg{k}.pre", f"hg{k}.c3")
-            run(f"hg{k}.conv4", hg + ".conv4", f"hg{k}.c3", f"hg{k}.c4")
-            run(f"hg{k}.conv5", hg + ".conv5", f"hg{k}.c4", f"hg{k}.post", res=presqu)
-            run(f"hg{k}.conv6", hg + ".conv6", f"hg{k}.post", f"out{k}", res="cost0")
-        prev = None
-        for k in (1, 2, 3):
-            run(f"classif{k}.0", f"classif{k}.0", f"out{k}", f"cls_t{k}")
-            p[f"classif{k}.2"].run(t[f"cls_t{k}"], W16[f"classif{k}.2"], None, None, t[f"costk{k}"], prev)
-            prev = t[f"costk{k}"]
-        return t["costk1"], t["costk2"], t["costk3"]
 
     def _use_f16(self, training):
         mode = getattr(self.model, "regressor_storage", "f32")
@@ -854,19 +834,19 @@ class PSMNetRuntime:
             z = torch.empty(0, H, W, dtype=torch.float32, device=self.device)
             return (z, z.clone(), z.clone()) if training else z       # empty ROI batch (reference: disprcnn3d.py:272-275)
         if not self._use_f16(training) and self._use_s16(training, (mx - mn) // 4, Hp, Wp):
-            ws = self._ws3d_s16(N, (mx - mn) // 4, Hp, Wp)
+            ws = self._ws3d(_SplitF16, N, (mx - mn) // 4, Hp, Wp)
             self._stamp(ws)
             ws["t"]["featL"].from_dense(fl)             # (the two layout converters need no weights: they are launched BEFORE the parameter-version
             ws["t"]["featR"].from_dense(fr)             #  check -- 0.14 ms of host time that would otherwise sit in front of an idle GPU, §3.8)
             Wt = self._compile()
-            return self._heads(self._regress_s16(ws, Wt, mn // 4), N, H, W, mx, mn, False)
+            return self._heads(self._regress(ws, Wt, mn // 4), N, H, W, mx, mn, False)
         Wt = self._compile()
         if self._use_f16(training):
-            ws = self._ws3d16(N, (mx - mn) // 4, Hp, Wp)
+            ws = self._ws3d(_Blocked16, N, (mx - mn) // 4, Hp, Wp)
             self._stamp(ws)
             self._costvol16(ws, mn, mx, fl.contiguous(), fr.contiguous())
-            return self._heads(self._regress16(ws, Wt), N, H, W, mx, mn, False)
-        ws = self._ws3d(N, (mx - mn) // 4, Hp, Wp)
+            return self._heads(self._regress(ws, Wt), N, H, W, mx, mn, False)
+        ws = self._ws3d(_Blocked32, N, (mx - mn) // 4, Hp, Wp)
         self._stamp(ws)
         cv = None
         if self._fuse_costvol(ws, training):
@@ -881,71 +861,60 @@ class PSMNetRuntime:
         return self._heads(costs, N, H, W, mx, mn, training)
 
     # ------------------------------------------------------------------ 2D feature CNN
-    def _ws2d(self, N, H, W, side=None):
-        key = self._slotted(("2d", N, H, W) if side is None else ("2d", N, H, W, side))
+    def _ws2d(self, N, H, W, side=None, f16=False):
+        """The 2D CNN's workspace on fp32 Blocked tensors (channel blocks of 16) or, f16, on Blocked16 tensors (blocks of 32; BASELINE
+        configs[3], eval only): schedule.trunk_sites() + the SPP / lastconv tail."""
+        tag = "2d16" if f16 else "2d"
+        key = self._slotted((tag, N, H, W) if side is None else (tag, N, H, W, side))
         ws = self._ws_get(key)
         if ws is not None:
             return ws
         if H % 4 or W % 4 or H // 4 < 56 or W // 4 < 56:
             raise ValueError("PSMNet needs H,W multiples of 4 and >= 224 (fixed AvgPool2d(56), reference submodule.py:76)")
-        pool = self._pool_for(self._slotted(("2d", H, W, side)), N)
+        pool = self._pool_for(self._slotted((tag, H, W) if f16 else (tag, H, W, side)), N)
         names = iter(range(1 << 30))
-        B2 = lambda c, h, w, pad=1: pool.blocked(("t", next(names)), N, c, 1, h, w, 0, pad, pad)   # allocation order is deterministic
-        H2, W2, H4, W4 = H // 2, W // 2, H // 4, W // 4
+        if f16:
+            B2 = lambda c, h, w, pad=1: pool.blocked16(("t16", next(names)), N, c, 1, h, w, 0, pad, pad)
+            plan, Slice, cb = E.plan_conv2d16, E.Blocked16Slice, 32
+        else:
+            B2 = lambda c, h, w, pad=1: pool.blocked(("t", next(names)), N, c, 1, h, w, 0, pad, pad)   # allocation order is deterministic
+            plan, Slice, cb = E.plan_conv2d, E.BlockedSlice, 16
+        hw = ((H, W), (H // 2, W // 2), (H // 4, W // 4))
+        parts = {TRUNK.raw: CONCAT[0], TRUNK.skip: CONCAT[1]}     # output_raw, output_skip are written into the concat
         t, p = {}, {}
         t["img"] = B2(3, H, W)
-        t["f0"], t["f1"], t["f2"] = B2(32, H2, W2), B2(32, H2, W2), B2(32, H2, W2)
-        p["fe.firstconv.0"] = E.plan_conv2d(t["img"], t["f0"], 3, 2, 1, 1, 32, True)
-        p["fe.firstconv.2"] = E.plan_conv2d(t["f0"], t["f1"], 3, 1, 1, 1, 32, True)
-        p["fe.firstconv.4"] = E.plan_conv2d(t["f1"], t["f2"], 3, 1, 1, 1, 32, True)
-        t["cat"] = B2(320, H4, W4)
+        for s in TRUNK.stem:
+            t[s.y] = B2(s.cout, *hw[s.level])
+        for s in TRUNK.stem:                                        # (launched by _features / _features16 themselves: not in sched)
+            p[s.wname] = plan(t[s.x], t[s.y], s.k, s.stride, s.pad, s.dilation, s.cout, s.relu)
+        t["cat"] = B2(320, *hw[2])
         sched = []   # (plan key, weight key, x, y, res)
-        cur, cur_c, cur_hw = "f2", 32, (H2, W2)
-        for name, planes, nblk, stride, dil in TRUNK_STAGES:
-            pad = 2 if name in ("layer3", "layer4") else 1      # tensors read by the dilated layer4 carry halo 2
-            for b in range(nblk):
-                s = stride if b == 0 else 1
-                hw = (cur_hw[0] // s, cur_hw[1] // s)
-                u = f"fe.{name}.{b}"
-                mid = u + ".mid"
-                t[mid] = B2(planes, hw[0], hw[1], pad)
-                p[u + ".conv1"] = E.plan_conv2d(t[cur], t[mid], 3, s, 1 if dil == 1 else dil, dil, planes, True)
-                sched.append((u + ".conv1", u + ".conv1", cur, mid, None))
-                res = cur
-                if (u + ".down") in self._w:
-                    t[u + ".sc"] = B2(planes, hw[0], hw[1], pad)
-                    p[u + ".down"] = E.plan_conv2d(t[cur], t[u + ".sc"], 1, s, 0, 1, planes, False)
-                    sched.append((u + ".down", u + ".down", cur, u + ".sc", None))
-                    res = u + ".sc"
-                last = b == nblk - 1
-                if name == "layer2" and last:
-                    t[u + ".out"] = E.BlockedSlice(t["cat"], 0, 64)        # output_raw -> channels 0..63 of the concat
-                elif name == "layer4" and last:
-                    t[u + ".out"] = E.BlockedSlice(t["cat"], 4, 128)       # output_skip -> channels 64..191
-                else:
-                    t[u + ".out"] = B2(planes, hw[0], hw[1], pad)
-                p[u + ".conv2"] = E.plan_conv2d(t[mid], t[u + ".out"], 3, 1, 1 if dil == 1 else dil, dil, planes, False)
-                sched.append((u + ".conv2", u + ".conv2", mid, u + ".out", res))   # out += x, no trailing relu
-                cur, cur_c, cur_hw = u + ".out", planes, hw
-        skip = cur
-        return self._ws_put(key, self._ws2d_tail(t, p, B2, pool, sched, skip, H4, W4))
+        for s in TRUNK.blocks:
+            if s.y in parts:
+                _, off, ch = parts[s.y]
+                t[s.y] = Slice(t["cat"], off // cb, ch)
+            else:
+                t[s.y] = B2(s.cout, *hw[s.level], s.halo)
+            p[s.wname] = plan(t[s.x], t[s.y], s.k, s.stride, s.pad, s.dilation, s.cout, s.relu)
+            sched.append((s.wname, s.wname, s.x, s.y, s.res))
+        return self._ws_put(key, self._ws2d_tail(t, p, B2, plan, cb, pool, sched, TRUNK.skip, *hw[2]))
 
     @staticmethod
-    def _ws2d_tail(t, p, B2, pool, sched, skip, H4, W4):
-        """The SPP branches and lastconv of a 2D workspace (shared by the fp32 and the split-f16 schedules)."""
-        # SPP: concat order (raw, skip, b4, b3, b2, b1) -> channel blocks 0-3, 4-11, 12-13, 14-15, 16-17, 18-19
-        slot = {"branch4": 12, "branch3": 14, "branch2": 16, "branch1": 18}
+    def _ws2d_tail(t, p, B2, plan, cb, pool, sched, skip, H4, W4):
+        """The SPP branches and lastconv of a 2D workspace (shared by the fp32, the fp16-storage and the split-f16 schedules); cb: channels
+        per block of the storage.  Concat order (raw, skip, b4, b3, b2, b1), submodule.py:134-135."""
+        slot = concat_slots(cb)
         spp = []
         for name, k in SPP_BRANCHES:
             oh, ow = H4 // k, W4 // k
             t[name + ".pool"] = B2(128, oh, ow, 0)
             t[name + ".conv"] = B2(32, oh, ow, 0)
-            p["fe." + name] = E.plan_conv2d(t[name + ".pool"], t[name + ".conv"], 1, 1, 0, 1, 32, True)
+            p["fe." + name] = plan(t[name + ".pool"], t[name + ".conv"], 1, 1, 0, 1, 32, True)
             spp.append((name, k, oh, ow, slot[name]))
         t["last0"] = B2(128, H4, W4, 0)
         t["feat"] = B2(32, H4, W4, 1)
-        p["fe.lastconv.0"] = E.plan_conv2d(t["cat"], t["last0"], 3, 1, 1, 1, 128, True)
-        p["fe.lastconv.2"] = E.plan_conv2d(t["last0"], t["feat"], 1, 1, 0, 1, 32, False)
+        p["fe.lastconv.0"] = plan(t["cat"], t["last0"], 3, 1, 1, 1, 128, True)
+        p["fe.lastconv.2"] = plan(t["last0"], t["feat"], 1, 1, 0, 1, 32, False)
         return dict(t=t, p=p, pool=pool, sched=sched, spp=spp, skip=skip, dims=(H4, W4),
                     flops=sum(pl.flops for pl in p.values()) + sum(e[1].flops for e in sched if e[0] == "s16"))
 
@@ -990,25 +959,33 @@ class PSMNetRuntime:
         sched = []
         plans = {}
 
-        def s16(wname, x, y, res, cin, cout, h, w, relu):
+        def s16(cin, cout, h, w, wname, x, y, res, relu):
             k = (cin, cout, h, w, relu)
             if k not in plans:
                 plans[k] = E.ConvPlanS16(N, cin, cout, 1, h, w, relu, device=self.device, kind="2d")
             sched.append(("s16", plans[k], wname, x, y, res))
 
+        def blocks(stage, first, conv, cur, free):
+            """The residual blocks first.. of a stage on three rotating maps: conv1 into a free map, conv2 + the block's input into the
+            other; conv(weight key, x, y, res, relu) plans and schedules one layer.  -> (cur, free)"""
+            name, _, nblk, _, _ = stage
+            for b in range(first, nblk):
+                u = f"fe.{name}.{b}"
+                mid, out = free
+                conv(u + ".conv1", cur, mid, None, True)
+                conv(u + ".conv2", mid, out, cur, False)
+                cur, free = out, [mid, cur]
+            return cur, free
+
+        slot = concat_slots(16)
+        half, quart64, quart128 = (functools.partial(s16, c, c, h, w) for c, h, w in ((32, H2, W2), (64, H4, W4), (128, H4, W4)))
         # firstconv[2], [4] and layer1: 32 channels at half resolution, three rotating maps
         for i in range(3):
             t[f"a{i}"] = S2(f"a{i}", 32, H2, W2)
         sched.append(("to16", "f0", "a0"))
-        s16("fe.firstconv.2", "a0", "a1", None, 32, 32, H2, W2, True)
-        s16("fe.firstconv.4", "a1", "a2", None, 32, 32, H2, W2, True)
-        cur, free = "a2", ["a0", "a1"]
-        for b in range(TRUNK_STAGES[0][2]):
-            u = f"fe.layer1.{b}"
-            mid, out = free
-            s16(u + ".conv1", cur, mid, None, 32, 32, H2, W2, True)
-            s16(u + ".conv2", mid, out, cur, 32, 32, H2, W2, False)
-            cur, free = out, [mid, cur]
+        half("fe.firstconv.2", "a0", "a1", None, True)
+        half("fe.firstconv.4", "a1", "a2", None, True)
+        cur, free = blocks(TRUNK_STAGES[0], 0, half, "a2", ["a0", "a1"])
         # layer2: the stride-2 conv and the 1x1 downsample of its first block stay fp32
         t["l2in"] = B2(32, H2, W2)
         t["l2mid"], t["l2sc"] = B2(64, H4, W4), B2(64, H4, W4)
@@ -1022,16 +999,10 @@ class PSMNetRuntime:
             t[f"b{i}"] = S2(f"b{i}", 64, H4, W4)
         sched.append(("to16", "l2mid", "b0"))
         sched.append(("to16", "l2sc", "b1"))
-        s16(u + ".conv2", "b0", "b2", "b1", 64, 64, H4, W4, False)
-        cur, free = "b2", ["b0", "b1"]
-        for b in range(1, TRUNK_STAGES[1][2]):
-            u = f"fe.layer2.{b}"
-            mid, out = free
-            s16(u + ".conv1", cur, mid, None, 64, 64, H4, W4, True)
-            s16(u + ".conv2", mid, out, cur, 64, 64, H4, W4, False)
-            cur, free = out, [mid, cur]
+        quart64(u + ".conv2", "b0", "b2", "b1", False)
+        cur, free = blocks(TRUNK_STAGES[1], 1, quart64, "b2", ["b0", "b1"])
         # output_raw -> channels 0..63 of the concat (fp32), which is also the input of layer3's 1x1 downsample
-        t["raw"] = E.BlockedSlice(t["cat"], 0, 64)
+        t["raw"] = E.BlockedSlice(t["cat"], slot["raw"], 64)
         sched.append(("to32", cur, "raw"))
         raw16 = cur                                            # (its RS16 map stays: layer3 rotates its own three maps)
         t["l3sc"] = B2(128, H4, W4)
@@ -1041,17 +1012,11 @@ class PSMNetRuntime:
         for i in range(3):
             t[f"c{i}"] = S2(f"c{i}", 128, H4, W4)
         sched.append(("to16", "l3sc", "c1"))
-        s16(u + ".conv1", cur, "c0", None, 64, 128, H4, W4, True)
-        s16(u + ".conv2", "c0", "c2", "c1", 128, 128, H4, W4, False)
-        cur, free = "c2", ["c0", "c1"]
-        for b in range(1, TRUNK_STAGES[2][2]):
-            u = f"fe.layer3.{b}"
-            mid, out = free
-            s16(u + ".conv1", cur, mid, None, 128, 128, H4, W4, True)
-            s16(u + ".conv2", mid, out, cur, 128, 128, H4, W4, False)
-            cur, free = out, [mid, cur]
+        s16(64, 128, H4, W4, u + ".conv1", cur, "c0", None, True)
+        quart128(u + ".conv2", "c0", "c2", "c1", False)
+        cur, free = blocks(TRUNK_STAGES[2], 1, quart128, "c2", ["c0", "c1"])
         # layer4 (dilation 2): the same kernel's dilated form where the map is a multiple of 56 rows, else fp32 on tensors with halo 2
-        name, planes, nblk, stride, dil = TRUNK_STAGES[3]
+        dil = TRUNK_STAGES[3][4]
         if E.s16_supported(128, 128, 1, H4, W4, "2d", dil):
             plans4 = {}
 
@@ -1059,39 +1024,32 @@ class PSMNetRuntime:
                 if relu not in plans4:
                     plans4[relu] = E.ConvPlanS16(N, 128, 128, 1, H4, W4, relu, device=self.device, kind="2d", dil=dil)
                 sched.append(("s16", plans4[relu], wname, x, y, res))
-            for b in range(nblk):
-                u = f"fe.{name}.{b}"
-                mid, out = free
-                s16d(u + ".conv1", cur, mid, None, True)
-                s16d(u + ".conv2", mid, out, cur, False)
-                cur, free = out, [mid, cur]
-            t["skip"] = E.BlockedSlice(t["cat"], 4, 128)       # output_skip -> channels 64..191 of the concat
+            cur, free = blocks(TRUNK_STAGES[3], 0, s16d, cur, free)
+            t["skip"] = E.BlockedSlice(t["cat"], slot["skip"], 128)       # output_skip -> channels 64..191 of the concat
             sched.append(("to32", cur, "skip"))
             last16 = (raw16, cur, free[0], free[1])            # RS16 maps of raw and skip, two free 128-channel maps
             cur = "skip"
         else:
+            # the fp32 sites of layer4 as in _ws2d, reading the converted output of layer3 (l4in) in place of its fp32 tensor
             last16 = None
             t["l4in"] = B2(128, H4, W4, 2)
             sched.append(("to32", cur, "l4in"))
-            cur = "l4in"
-            for b in range(nblk):
-                u = f"fe.{name}.{b}"
-                mid = u + ".mid"
-                t[mid] = B2(planes, H4, W4, 2)
-                p[u + ".conv1"] = E.plan_conv2d(t[cur], t[mid], 3, 1, dil, dil, planes, True)
-                sched.append((u + ".conv1", u + ".conv1", cur, mid, None))
-                t[u + ".out"] = E.BlockedSlice(t["cat"], 4, 128) if b == nblk - 1 else B2(planes, H4, W4, 2)
-                p[u + ".conv2"] = E.plan_conv2d(t[mid], t[u + ".out"], 3, 1, dil, dil, planes, False)
-                sched.append((u + ".conv2", u + ".conv2", mid, u + ".out", cur))
-                cur = u + ".out"
-        ws = self._ws2d_tail(t, p, B2, pool, sched, cur, H4, W4)
+            layer4 = [s for s in TRUNK.blocks if s.wname.startswith("fe.layer4.")]
+            rename = {layer4[0].x: "l4in"}
+            for s in layer4:
+                x, res = rename.get(s.x, s.x), rename.get(s.res, s.res)
+                t[s.y] = E.BlockedSlice(t["cat"], slot["skip"], 128) if s.y == TRUNK.skip else B2(s.cout, H4, W4, s.halo)
+                p[s.wname] = E.plan_conv2d(t[x], t[s.y], s.k, s.stride, s.pad, s.dilation, s.cout, s.relu)
+                sched.append((s.wname, s.wname, x, s.y, res))
+            cur = TRUNK.skip
+        ws = self._ws2d_tail(t, p, B2, E.plan_conv2d, 16, pool, sched, cur, H4, W4)
         ws["s16"] = True
         if last16 is not None and E.LASTCONV_S16["enabled"]:
             # lastconv[0] (3x3, 320 -> 128, submodule.py:125-128; 10.5 % of the CNN's FLOPs) as three chained split-f16 launches over the
             # concat's parts -- raw (64), skip (128), the four upsampled SPP branches (128) -- each adding the previous partial sum as its
             # residual (BN is affine: its scale goes to every part, its shift to the first, the ReLU to the last).  The parts' RS16 maps exist
             # already (raw, skip) or are converted from the concat's branch slice; the fp32 concat is still what the 1x1 / pooling kernels read.
-            t["br32"] = E.BlockedSlice(t["cat"], 12, 128)
+            t["br32"] = E.BlockedSlice(t["cat"], slot["branch4"], 128)
             t["br16"] = S2("br16", 128, H4, W4)
             raw16, skip16, lp0, lp1 = last16
             ws["last16"] = dict(
@@ -1179,69 +1137,6 @@ class PSMNetRuntime:
         return t["feat"]
 
     # ------------------------------------------------------------------ fp16-storage 2D feature CNN (BASELINE configs[3]; eval only)
-    def _ws2d16(self, N, H, W):
-        """The schedule of _ws2d on Blocked16 tensors.  The 320-channel concat is 10 blocks of 32: raw (64) -> blocks 0-1, skip (128) ->
-        2-5, branch4..branch1 (32 each) -> 6, 7, 8, 9 (concatenation order of submodule.py:134-135)."""
-        key = self._slotted(("2d16", N, H, W))
-        ws = self._ws_get(key)
-        if ws is not None:
-            return ws
-        if H % 4 or W % 4 or H // 4 < 56 or W // 4 < 56:
-            raise ValueError("PSMNet needs H,W multiples of 4 and >= 224 (fixed AvgPool2d(56), reference submodule.py:76)")
-        pool = self._pool_for(self._slotted(("2d16", H, W)), N)
-        names = iter(range(1 << 30))
-        B2 = lambda c, h, w, pad=1: pool.blocked16(("t16", next(names)), N, c, 1, h, w, 0, pad, pad)
-        H2, W2, H4, W4 = H // 2, W // 2, H // 4, W // 4
-        t, p = {}, {}
-        t["img"] = B2(3, H, W)
-        t["f0"], t["f1"], t["f2"] = B2(32, H2, W2), B2(32, H2, W2), B2(32, H2, W2)
-        p["fe.firstconv.0"] = E.plan_conv2d16(t["img"], t["f0"], 3, 2, 1, 1, 32, True)
-        p["fe.firstconv.2"] = E.plan_conv2d16(t["f0"], t["f1"], 3, 1, 1, 1, 32, True)
-        p["fe.firstconv.4"] = E.plan_conv2d16(t["f1"], t["f2"], 3, 1, 1, 1, 32, True)
-        t["cat"] = B2(320, H4, W4)
-        sched = []
-        cur, cur_hw = "f2", (H2, W2)
-        for name, planes, nblk, stride, dil in TRUNK_STAGES:
-            pad = 2 if name in ("layer3", "layer4") else 1      # tensors read by the dilated layer4 carry halo 2
-            for b in range(nblk):
-                s = stride if b == 0 else 1
-                hw = (cur_hw[0] // s, cur_hw[1] // s)
-                u = f"fe.{name}.{b}"
-                mid = u + ".mid"
-                t[mid] = B2(planes, hw[0], hw[1], pad)
-                p[u + ".conv1"] = E.plan_conv2d16(t[cur], t[mid], 3, s, 1 if dil == 1 else dil, dil, planes, True)
-                sched.append((u + ".conv1", cur, mid, None))
-                res = cur
-                if (u + ".down") in self._w:
-                    t[u + ".sc"] = B2(planes, hw[0], hw[1], pad)
-                    p[u + ".down"] = E.plan_conv2d16(t[cur], t[u + ".sc"], 1, s, 0, 1, planes, False)
-                    sched.append((u + ".down", cur, u + ".sc", None))
-                    res = u + ".sc"
-                last = b == nblk - 1
-                if name == "layer2" and last:
-                    t[u + ".out"] = E.Blocked16Slice(t["cat"], 0, 64)
-                elif name == "layer4" and last:
-                    t[u + ".out"] = E.Blocked16Slice(t["cat"], 2, 128)
-                else:
-                    t[u + ".out"] = B2(planes, hw[0], hw[1], pad)
-                p[u + ".conv2"] = E.plan_conv2d16(t[mid], t[u + ".out"], 3, 1, 1 if dil == 1 else dil, dil, planes, False)
-                sched.append((u + ".conv2", mid, u + ".out", res))
-                cur, cur_hw = u + ".out", hw
-        slot = {"branch4": 6, "branch3": 7, "branch2": 8, "branch1": 9}
-        spp = []
-        for name, k in SPP_BRANCHES:
-            oh, ow = H4 // k, W4 // k
-            t[name + ".pool"] = B2(128, oh, ow, 0)
-            t[name + ".conv"] = B2(32, oh, ow, 0)
-            p["fe." + name] = E.plan_conv2d16(t[name + ".pool"], t[name + ".conv"], 1, 1, 0, 1, 32, True)
-            spp.append((name, k, oh, ow, slot[name]))
-        t["last0"] = B2(128, H4, W4, 0)
-        t["feat"] = B2(32, H4, W4, 1)
-        p["fe.lastconv.0"] = E.plan_conv2d16(t["cat"], t["last0"], 3, 1, 1, 1, 128, True)
-        p["fe.lastconv.2"] = E.plan_conv2d16(t["last0"], t["feat"], 1, 1, 0, 1, 32, False)
-        ws = dict(t=t, p=p, pool=pool, sched=sched, spp=spp, skip=cur, dims=(H4, W4), flops=sum(pl.flops for pl in p.values()))
-        return self._ws_put(key, ws)
-
     def _features16(self, ws, W, images):
         """feature_extraction with fp16 storage (fp32 accumulation, BatchNorm folded in fp32): -> Blocked16 [N,32,H/4,W/4] (halo 1)."""
         from ... import _lib
@@ -1257,7 +1152,7 @@ class PSMNetRuntime:
         run("fe.firstconv.0", "img", "f0")
         run("fe.firstconv.2", "f0", "f1")
         run("fe.firstconv.4", "f1", "f2")
-        for name, x, y, res in ws["sched"]:
+        for _, name, x, y, res in ws["sched"]:
             run(name, x, y, res)
         skip, cat = t[ws["skip"]], t["cat"]
         H4, W4 = ws["dims"]
@@ -1301,29 +1196,29 @@ class PSMNetRuntime:
         Wt = self._compile()
         if self._use_f16(training):
             # fp32 2D feature CNN (its output is the cost volume's input), fp16-storage cost volume + 3D regressor
-            ws3 = self._ws3d16(N, (mx - mn) // 4, H // 4, W // 4)
+            ws3 = self._ws3d(_Blocked16, N, (mx - mn) // 4, H // 4, W // 4)
             if self._features_f16():
                 # fp16-storage 2D CNN as well (feature_storage = "f16"): blocked fp16 features straight into the fp16 cost volume
-                ws2 = self._ws2d16(2 * N, H, W)
+                ws2 = self._ws2d(2 * N, H, W, f16=True)
                 self._stamp(ws3, ws2)
                 feat = self._features16(ws2, Wt, torch.cat((left, right), 0))
                 self._costvol16(ws3, mn, mx, feat16=feat, right_first=N)
-                return self._heads(self._regress16(ws3, Wt), N, H, W, mx, mn, False)
+                return self._heads(self._regress(ws3, Wt), N, H, W, mx, mn, False)
             ws2 = self._ws2d_eval(2 * N, H, W)
             self._stamp(ws3, ws2)
             feat = self._features(ws2, Wt, (left, right))
             fv = feat.storage
             self._costvol16(ws3, mn, mx, fv, fv[N * feat.n_stride:], feat.ph)
-            return self._heads(self._regress16(ws3, Wt), N, H, W, mx, mn, False)
+            return self._heads(self._regress(ws3, Wt), N, H, W, mx, mn, False)
         if self._use_s16(training, (mx - mn) // 4, H // 4, W // 4):
-            ws3 = self._ws3d_s16(N, (mx - mn) // 4, H // 4, W // 4)
+            ws3 = self._ws3d(_SplitF16, N, (mx - mn) // 4, H // 4, W // 4)
             ws2 = self._ws2d_eval(2 * N, H, W)
             self._stamp(ws3, ws2)
             feat = self._features(ws2, Wt, (left, right))
             ws3["t"]["featL"].from_blocked(feat, 0)
             ws3["t"]["featR"].from_blocked(feat, N)
-            return self._heads(self._regress_s16(ws3, Wt, mn // 4), N, H, W, mx, mn, False)
-        ws3 = self._ws3d(N, (mx - mn) // 4, H // 4, W // 4)
+            return self._heads(self._regress(ws3, Wt, mn // 4), N, H, W, mx, mn, False)
+        ws3 = self._ws3d(_Blocked32, N, (mx - mn) // 4, H // 4, W // 4)
         cv = None
         if training:
             # the reference runs feature_extraction(left) and feature_extraction(right) as two calls (stackhourglass.py:112-113):

@@ -154,6 +154,30 @@ def test_config_a_f16_vs_fp32_oracle(dev):
         m.train().forward_from_features(fl.to(dev), fr.to(dev), (112, 112))
 
 
+def test_config_a_f16_materialised_cost_volume_vs_fp32_oracle(dev):
+    """The fp16-storage regressor with engine.COSTVOL16_FUSED off -- the workspace holds the 64-channel fp16 volume, dres0[0] is a plain
+    conv16 plan -- a branch no other test takes through the runtime (the layer itself: test_costvol_fused_first_layer_is_bit_identical).
+    Config A's shape at two units, so the bound is that of test_config_a_f16_vs_fp32_oracle: mean <= 5e-2 px."""
+    from disprcnn_amd import engine as E
+    sd = state_for("A")
+    fl, fr = synth.synth_features(2, 32, 28, 28, tag="f16A")
+    assert E.COSTVOL16_FUSED["enabled"]
+    E.COSTVOL16_FUSED["enabled"] = False
+    try:
+        m = _model(dev, "A", 48, 0, "f16")
+        with torch.no_grad():
+            got = m.forward_from_features(fl.to(dev), fr.to(dev), (112, 112)).cpu()
+    finally:
+        E.COSTVOL16_FUSED["enabled"] = True
+    ws = m._rt._ws[("3d16", 2, 12, 28, 28)]
+    assert "cost" in ws["t"] and "pair" not in ws["t"] and ws["p"]["dres0.0"].costvol_lo4 is None
+    with torch.no_grad():
+        ref = O.psmnet_from_features(sd, fl, fr, 48, 0, 112, 112)
+    err = (got - ref).abs()
+    print("Config A f16 storage, materialised volume: mean/max |err| px", err.mean().item(), err.max().item())
+    assert err.mean().item() <= 5e-2 and torch.isfinite(got).all()
+
+
 # Measured on MI355X (round 5, all 64 ROIs, D = 96) against the CPU fp32 oracle, mean / max |err| px:
 #     fp16-STORAGE regressor: sharp set "B" 0.0514 / 1.15, tempered set "Bt" 0.0050 / 0.061;   default split-f16 path: 2.6e-4 / 7.7e-3 and 2.4e-5 / 2.7e-4.
 # SURVEY 8c proposed 5e-2 for the fp16 mode: the tempered set (classif*.2 weights x 0.1, "realistic softmax entropy") is 10x inside it, the

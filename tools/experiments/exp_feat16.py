@@ -48,5 +48,5 @@ v[:, 0, 0] = v32[:, :, 0].permute(0, 2, 3, 1, 4).reshape(N_, Hp, Wp, 32).half()
 ws3 = [w for k, w in rt._ws.items() if k[0] == "3d16"][0]
 with torch.no_grad():
     E.cost_volume16_from16(f16t, 4, ws3["t"]["cost"], -12, 12)
-    c = rt._heads(rt._regress16(ws3, rt._compile()), 4, 224, 224, 48, -48, False).cpu()
+    c = rt._heads(rt._regress(ws3, rt._compile()), 4, 224, 224, 48, -48, False).cpu()
 print("disp err with fp32 features rounded to f16 through the new cost-volume kernel:", (c - ref).abs().mean().item())
