@@ -4,7 +4,9 @@ PyTorch is used for device memory, streams and parameter storage only; all arith
 the hot path runs in libdisprcnn_hip.so through the C ABI (include/disprcnn_hip.h).
 """
 import ctypes as C
+import functools
 import math
+from collections import namedtuple
 
 import torch
 
@@ -25,6 +27,20 @@ def _stream_ptr(device):
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _timing_start(device):
+    """The start event of a TIMING bracket.  Callers: `e0 = None if TIMING is None else _timing_start(dev)` before the launch and
+    `if e0 is not None: _timing_stop(...)` after it (TIMING is read at call time: bench.py and the tests assign the module attribute)."""
+    e0 = torch.cuda.Event(enable_timing=True)
+    e0.record(torch.cuda.current_stream(device))
+    return e0
+
+
+def _timing_stop(e0, device, kname, flops):
+    e1 = torch.cuda.Event(enable_timing=True)
+    e1.record(torch.cuda.current_stream(device))
+    TIMING.append((kname, flops, e0, e1))
 
 
 def require_gpu(t, what):
@@ -253,63 +269,36 @@ def pack_weight_t16(w, transposed=False):
     return wp.view(K, cb, CB, cout_pad).permute(0, 1, 3, 2).contiguous()
 
 
-def pack_weight_wino(w, transposed=False, flip=False):
-    """3x3x3 weights [Cout,Cin,3,3,3] (or [Cin,Cout,...] with transposed; flip reverses the taps) -> Winograd F(2,3)^3
-    transformed [64 frequency points][cb_in][cout_pad][16] (drc_pack_weights_wino): the packing of wino3d.hip."""
+# The Winograd-transformed weights: packing -> (weight dims, frequency points, cout padding).  Every packing is
+# [points][cb_in][cout_pad][16] fp32, written by the C entry drc_pack_weights_<packing>:
+_WINO_PACKINGS = {
+    "wino": (5, 64, 16),        # F(2,3)^3 of a 3x3x3 kernel: wino3d.hip
+    "wino_rb": (5, 64, 32),     # ... as [64][cb_in][cout tile][ch / 4][cout % 16][ch % 4], a (point, channel block, cout tile) unit being the 1 KiB an LDS-DMA instruction copies in lane order: wino3d_rb.hip
+    "wino2d": (4, 16, 16),      # F(2,3)^2 of a 3x3 kernel: wino2d.hip
+    "wino2d_rb": (4, 16, 32),   # ... in the packing of wino3d_rb.hip's 2D form
+}
+
+
+def _pack_wino(kind, w, transposed=False, flip=False):
+    """[Cout,Cin,*k] (or [Cin,Cout,*k] with transposed; flip reverses the taps) -> the transformed weights of _WINO_PACKINGS[kind]."""
+    dims, points, pad = _WINO_PACKINGS[kind]
     w = w.detach().contiguous().float()
-    require_gpu(w, "pack_weight_wino")
-    if w.dim() != 5 or tuple(w.shape[2:]) != (3, 3, 3):
-        raise ValueError("pack_weight_wino expects a 3x3x3 kernel")
+    require_gpu(w, "pack_weight_" + kind)
+    if w.dim() != dims or tuple(w.shape[2:]) != (3,) * (dims - 2):
+        raise ValueError("pack_weight_%s expects a %s kernel" % (kind, "x".join("3" * (dims - 2))))
     a, b = w.shape[:2]
     cout, cin = (b, a) if transposed else (a, b)
-    out = torch.empty(64, (cin + CB - 1) // CB, cout_pad_of(cout), 16, dtype=torch.float32, device=w.device)
-    st = _lib.lib().drc_pack_weights_wino(_ptr(w), cout, cin, int(transposed), int(flip), _ptr(out), _stream_ptr(w.device))
-    _lib.check(st, "drc_pack_weights_wino")
+    out = torch.empty(points, (cin + CB - 1) // CB, (cout + pad - 1) // pad * pad, 16, dtype=torch.float32, device=w.device)
+    entry = "drc_pack_weights_" + kind
+    st = getattr(_lib.lib(), entry)(_ptr(w), cout, cin, int(transposed), int(flip), _ptr(out), _stream_ptr(w.device))
+    _lib.check(st, entry)
     return out
 
 
-def pack_weight_wino_rb(w, transposed=False, flip=False):
-    """The same transformed weights in the packing of wino3d_rb.hip: [64][cb_in][cout tile][ch / 4][cout % 16][ch % 4] (cout padded
-    to 32) -- a (frequency point, channel block, cout tile) unit is the 1 KiB an LDS-DMA instruction copies in lane order."""
-    w = w.detach().contiguous().float()
-    require_gpu(w, "pack_weight_wino_rb")
-    if w.dim() != 5 or tuple(w.shape[2:]) != (3, 3, 3):
-        raise ValueError("pack_weight_wino_rb expects a 3x3x3 kernel")
-    a, b = w.shape[:2]
-    cout, cin = (b, a) if transposed else (a, b)
-    out = torch.empty(64, (cin + CB - 1) // CB, (cout + 31) // 32 * 32, 16, dtype=torch.float32, device=w.device)
-    st = _lib.lib().drc_pack_weights_wino_rb(_ptr(w), cout, cin, int(transposed), int(flip), _ptr(out), _stream_ptr(w.device))
-    _lib.check(st, "drc_pack_weights_wino_rb")
-    return out
-
-
-def pack_weight_wino2d_rb(w, transposed=False, flip=False):
-    """The 2D transformed weights in the packing of wino3d_rb.hip's 2D form: [16][cb_in][cout tile][ch / 4][cout % 16][ch % 4]."""
-    w = w.detach().contiguous().float()
-    require_gpu(w, "pack_weight_wino2d_rb")
-    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
-        raise ValueError("pack_weight_wino2d_rb expects a 3x3 kernel")
-    a, b = w.shape[:2]
-    cout, cin = (b, a) if transposed else (a, b)
-    out = torch.empty(16, (cin + CB - 1) // CB, (cout + 31) // 32 * 32, 16, dtype=torch.float32, device=w.device)
-    st = _lib.lib().drc_pack_weights_wino2d_rb(_ptr(w), cout, cin, int(transposed), int(flip), _ptr(out), _stream_ptr(w.device))
-    _lib.check(st, "drc_pack_weights_wino2d_rb")
-    return out
-
-
-def pack_weight_wino2d(w, transposed=False, flip=False):
-    """3x3 weights [Cout,Cin,3,3] (or [Cin,Cout,3,3] with transposed; flip reverses the taps) -> Winograd F(2,3)^2 transformed
-    [16 frequency points][cb_in][cout_pad][16] (drc_pack_weights_wino2d): the packing of wino2d.hip."""
-    w = w.detach().contiguous().float()
-    require_gpu(w, "pack_weight_wino2d")
-    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
-        raise ValueError("pack_weight_wino2d expects a 3x3 kernel")
-    a, b = w.shape[:2]
-    cout, cin = (b, a) if transposed else (a, b)
-    out = torch.empty(16, (cin + CB - 1) // CB, cout_pad_of(cout), 16, dtype=torch.float32, device=w.device)
-    st = _lib.lib().drc_pack_weights_wino2d(_ptr(w), cout, cin, int(transposed), int(flip), _ptr(out), _stream_ptr(w.device))
-    _lib.check(st, "drc_pack_weights_wino2d")
-    return out
+pack_weight_wino = functools.partial(_pack_wino, "wino")
+pack_weight_wino_rb = functools.partial(_pack_wino, "wino_rb")
+pack_weight_wino2d = functools.partial(_pack_wino, "wino2d")
+pack_weight_wino2d_rb = functools.partial(_pack_wino, "wino2d_rb")
 
 
 def _deconv_tap_order():
@@ -364,16 +353,13 @@ def stem_conv(images, w_packed, scale, shift, y, relu=True, unit0=0):
     if scale.numel() < cout_pad or shift.numel() < cout_pad or scale.dtype != torch.float32 or shift.dtype != torch.float32:
         raise ValueError("stem_conv: scale / shift must be fp32 vectors of at least cout_pad entries")
     x = images.contiguous()
-    if TIMING is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(torch.cuda.current_stream(y.device))
+    e0 = None if TIMING is None else _timing_start(y.device)
     st = _lib.lib().drc_conv2d_k3s2_stem_fwd(_ptr(x), n, H, W, _ptr(w_packed), w_packed.shape[1], _ptr(scale), _ptr(shift), _ptr(y.storage),
                                              y.n_stride, y.cb_stride, y.h_stride, y.interior_off + unit0 * y.n_stride, y.H, y.W, int(relu),
                                              _stream_ptr(y.device))
     _lib.check(st, "drc_conv2d_k3s2_stem_fwd")
-    if TIMING is not None:
-        e1.record(torch.cuda.current_stream(y.device))
-        TIMING.append(("stemconv_kernel", 2 * n * y.H * y.W * 27 * cout_pad, e0, e1))
+    if e0 is not None:
+        _timing_stop(e0, y.device, "stemconv_kernel", 2 * n * y.H * y.W * 27 * cout_pad)
 
 
 def pack_conv_weight(w, transposed=False):
@@ -487,20 +473,70 @@ def choose_tile(OH, OW, in_mul, span_h, span_w, max_slots=MAX_SLOTS):
     return best[1], best[2], best[3]
 
 
-class ConvPlan:
-    """A fully resolved tapconv launch: geometry, tap classes, tile choice.  Pointers are patched per call."""
+def fill_tap_classes(p, classes):
+    """Write the tap-grid classes into a DrcTapconvParams; returns the number of taps."""
+    p.n_classes = len(classes)
+    for ci, c in enumerate(classes):
+        k = p.cls[ci]
+        k.nd, k.nh, k.nw = c["n"]
+        k.dd0, k.dh0, k.dw0 = c["first"]
+        k.sd, k.sh, k.sw = c["step"]
+        k.wbase = c["wbase"]
+        k.wsd, k.wsh, k.wsw = c["wstep"]
+        k.out_off_d, k.out_off_h, k.out_off_w = c["off"]
+    return sum(c["n"][0] * c["n"][1] * c["n"][2] for c in classes)
 
-    def __init__(self, x, y, classes, in_mul, out_mul, grid_dhw, cout, relu, slide=False):
+
+# One record per fp32 convolution kernel a plan can launch.  entry: the C entry (p, [ct,] stream), takes_ct: whether it takes the plan's cout-tile
+# count; pack: the weight packing it reads; points / axis: a kernel that reads its weights from run()'s w16 argument expects `points` frequency
+# points or taps on that axis of it (0: it reads `w`); costvol: the entry of its fused cost-volume form (run_costvol); rs16: the entry of its
+# RS16-output form (run(y16=...)); flags: what ConvPlan's read-only properties of those names report.
+Kernel = namedtuple("Kernel", "entry takes_ct pack points axis flags costvol rs16", defaults=(None, None))
+KERNELS = {
+    "tapconv": Kernel("drc_tapconv_fwd", False, "tap", 0, 0, frozenset()),     # tapconv.hip: any tap grid, LDS-staged tiles
+    "tapdirect": Kernel("drc_tapconv3d_direct_fwd", True, "t16", 27, 0, frozenset({"slide", "direct"})),
+    "wino3d": Kernel("drc_conv3d_k3_wino_fwd", True, "wino", 64, 0, frozenset({"slide", "direct", "wino"}), costvol="drc_conv3d_k3_wino_costvol_fwd"),
+    "wino3d_rb": Kernel("drc_conv3d_k3_wino_rb_fwd", False, "wino_rb", 64, 0, frozenset({"slide", "direct", "wino", "rb"}),     # two waves per SIMD, row brick
+                        costvol="drc_conv3d_k3_wino_rb_costvol_fwd"),
+    "downdirect": Kernel("drc_conv3d_k3s2_direct_fwd", True, "t16", 27, 0, frozenset({"down", "direct"})),
+    "tapdeconv": Kernel("drc_deconv3d_k3s2_fwd", False, "tap", 0, 0, frozenset({"fused_deconv"})),
+    "deconvdirect": Kernel("drc_deconv3d_k3s2_direct_fwd", True, "deconv_direct", 27, 1, frozenset({"fused_deconv", "deconv_direct", "direct"}),
+                           rs16="drc_deconv3d_k3s2_direct_s16_fwd"),
+    "conv2ddirect": Kernel("drc_conv2d_k3_direct_fwd", True, "t16", 9, 0, frozenset({"c2d", "direct"})),
+    "wino2d": Kernel("drc_conv2d_k3_wino_fwd", True, "wino2d", 16, 0, frozenset({"c2d", "direct", "wino"})),
+    "wino2d_rb": Kernel("drc_conv2d_k3_wino_rb_fwd", False, "wino2d_rb", 16, 0, frozenset({"c2d", "direct", "wino", "rb"})),
+    "pointwise": Kernel("drc_conv2d_k1_fwd", False, "pw", 0, 0, frozenset({"pointwise"})),
+}
+_PACK16 = {"t16": lambda w, transposed, flip: pack_layouts(w, transposed, flip, want_tap=False)[1], "deconv_direct": pack_weight_deconv_direct,
+           "wino": pack_weight_wino, "wino_rb": pack_weight_wino_rb, "wino2d": pack_weight_wino2d, "wino2d_rb": pack_weight_wino2d_rb}
+
+
+def tapconv_choice(x, classes, in_mul, grid_dhw, cout, max_slots=MAX_SLOTS):
+    """The generic kernel's answer for a layer, which every plan starts from: (R, WT, LDS bytes per wave, kernel name)."""
+    OD, OH, OW = grid_dhw
+    span_h = max((c["n"][1] - 1) * c["step"][1] for c in classes)
+    span_w = max((c["n"][2] - 1) * c["step"][2] for c in classes)
+    R, WT, lds = choose_tile(OH, OW, in_mul, span_h, span_w, max_slots)
+    nvt = -(-(R * WT) // 16)
+    ct = cout_pad_of(cout) // 16
+    groups = x.N * OD * (-(-OH // R)) * (-(-OW // WT)) * len(classes)
+    CT = 4 if ct % 4 == 0 else (2 if ct % 2 == 0 else 1)
+    while CT > 1 and (groups * (ct // CT) < 2048 or nvt * CT > 16):      # mirrors drc_tapconv_fwd's choice
+        CT //= 2
+    return R, WT, lds, "tapconv_kernel<%d,%d>" % (nvt, CT)
+
+
+def _flag(name):
+    return property(lambda self: name in self.kernel.flags)
+
+
+class ConvPlan:
+    """A fully resolved fp32 convolution launch: geometry, tap classes, and what its plan_* function decided -- the kernel (a KERNELS record),
+    its cout tiles per wave `ct` (None for a kernel that takes none), the tile (R, WT) and the kernel's name `kname`; `lds` is the generic
+    kernel's LDS need (tapconv_choice), whichever kernel runs.  Pointers are patched per call."""
+
+    def __init__(self, x, y, classes, in_mul, out_mul, grid_dhw, cout, relu, kernel, kname, tile, lds, ct=None):
         p = DrcTapconvParams()
-        self.slide = slide
-        self.fused_deconv = False
-        self.down = False
-        self.pointwise = False
-        self.direct = False
-        self.wino = False
-        self.rb = False            # wino3d_rb.hip (two waves per SIMD, row brick) instead of wino3d.hip
-        self.c2d = False
-        self.deconv_direct = False
         OD, OH, OW = grid_dhw
         p.x_n_stride, p.x_cb_stride, p.x_d_stride, p.x_h_stride = x.n_stride, x.cb_stride, x.d_stride, x.h_stride
         p.y_n_stride, p.y_cb_stride, p.y_d_stride, p.y_h_stride = y.n_stride, y.cb_stride, y.d_stride, y.h_stride
@@ -508,84 +544,47 @@ class ConvPlan:
         p.N, p.OD, p.OH, p.OW = x.N, OD, OH, OW
         p.in_mul, p.out_mul = in_mul, out_mul
         p.cb_in = x.cb
-        p.cout_pad = (cout + CB - 1) // CB * CB
+        p.cout_pad = cout_pad_of(cout)
         p.relu = int(relu)
-        p.n_classes = len(classes)
-        span_h = max((c["n"][1] - 1) * c["step"][1] for c in classes)
-        span_w = max((c["n"][2] - 1) * c["step"][2] for c in classes)
-        R, WT, lds = choose_tile(OH, OW, in_mul, span_h, span_w, SLIDE["max_slots"] if slide else MAX_SLOTS)
-        p.R, p.WT = R, WT
+        p.R, p.WT = tile
         p.lds_bytes_per_wave = (lds + 1023) // 1024 * 1024
-        for ci, c in enumerate(classes):
-            k = p.cls[ci]
-            k.nd, k.nh, k.nw = c["n"]
-            k.dd0, k.dh0, k.dw0 = c["first"]
-            k.sd, k.sh, k.sw = c["step"]
-            k.wbase = c["wbase"]
-            k.wsd, k.wsh, k.wsw = c["wstep"]
-            k.out_off_d, k.out_off_h, k.out_off_w = c["off"]
-        self.p = p
-        self.device = x.device
-        ntaps = sum(c["n"][0] * c["n"][1] * c["n"][2] for c in classes)
+        ntaps = fill_tap_classes(p, classes)
+        self.p, self.device = p, x.device
+        self.kernel, self.kname, self.ct = kernel, kname, ct
+        self._ct_args = (ct,) if kernel.takes_ct else ()
         self.flops = 2 * x.N * OD * OH * OW * ntaps * x.C * cout       # algorithmic (unpadded channels, valid voxels)
-        nvt = -(-(R * WT) // 16)
-        ct = p.cout_pad // 16
-        groups = x.N * OD * (-(-OH // R)) * (-(-OW // WT)) * len(classes)
-        CT = 4 if ct % 4 == 0 else (2 if ct % 2 == 0 else 1)
-        while CT > 1 and (groups * (ct // CT) < 2048 or nvt * CT > 16):      # mirrors drc_tapconv_fwd's choice
-            CT //= 2
-        self.kname = self._generic_kname = "tapconv_kernel<%d,%d>" % (nvt, CT)
-        if slide:
-            # the sliding-window kernel gives every resident wave an equal share (>= 3 output slices) of the
-            # (cout group, column, slice) units: use it only when that still yields enough waves to fill the 1024 SIMDs
-            # (measured cross-over, tools/experiments/exp_conv.py)
-            self.slide_ct = SLIDE["ct"] if ct % SLIDE["ct"] == 0 else 1
-            cols = x.N * (-(-OH // R)) * (-(-OW // WT))
-            # small batches: with ONE cout tile per wave the LDS-free direct kernel still beats the generic kernel down to ~150 units
-            # (3x7x7 maps, 64->64: 47 vs 87 us at 64 ROIs, 45 vs 84 us at 16; at 128 ROIs two tiles per wave win, 75 vs 93 us)
-            self.slide_small_ok = OD >= SLIDE["min_od"] and cols * ct * OD >= SLIDE["min_units_ct1"]
-            if OD < SLIDE["min_od"] or cols * (ct // self.slide_ct) * OD // SLIDE["min_share"] < SLIDE["min_units"]:
-                self.slide = False
-            else:
-                self.kname = "tapslide_kernel<%d,%d>" % (nvt, self.slide_ct)
+
+    slide, fused_deconv, down, pointwise, direct, wino, rb, c2d, deconv_direct = map(
+        _flag, ("slide", "fused_deconv", "down", "pointwise", "direct", "wino", "rb", "c2d", "deconv_direct"))
 
     @property
     def needs_t16(self):
-        """True when this plan's kernel reads the [tap][cb][cout][16] packing (the LDS-free kernels) instead of the tap layout."""
-        return bool(self.direct and (self.slide or self.down or self.c2d or self.deconv_direct))
+        """True when this plan's kernel reads its weights from run()'s w16 argument (the LDS-free kernels) instead of the tap layout."""
+        return self.kernel.points > 0
 
     @property
     def pack_kind(self):
-        """Name of the weight packing pack16 returns (a layer may run under plans of several kinds: one packing is kept per kind)."""
-        if self.wino:
-            return ("wino2d_rb" if self.rb else "wino2d") if self.c2d else ("wino_rb" if self.rb else "wino")
-        return "deconv_direct" if self.deconv_direct else ("t16" if self.needs_t16 else "tap")
+        """Name of the weight packing pack16 returns (a layer may run under plans of several kinds: one packing is kept per kind); "tap" where
+        it returns None and the kernel reads run()'s `w` (pack_conv_weight)."""
+        return self.kernel.pack if self.kernel.points else "tap"
 
     def pack16(self, w, transposed=False, flip=False, kind=None):
-        """The weight packing this plan's LDS-free kernel reads (None when the plan runs an LDS-staged kernel)."""
-        if kind == "wino":
-            return pack_weight_wino(w, transposed, flip)
-        if self.wino and self.rb:
-            return pack_weight_wino2d_rb(w, transposed, flip) if self.c2d else pack_weight_wino_rb(w, transposed, flip)
-        if self.wino:
-            return pack_weight_wino2d(w, transposed, flip) if self.c2d else pack_weight_wino(w, transposed, flip)
-        if self.deconv_direct:
-            return pack_weight_deconv_direct(w, transposed, flip)
-        if self.needs_t16:
-            return pack_layouts(w, transposed, flip, want_tap=False)[1]
-        return None
+        """The weight packing this plan's LDS-free kernel reads (None when the plan runs an LDS-staged kernel); kind "wino": wino3d.hip's."""
+        pack = _PACK16.get("wino" if kind == "wino" else self.kernel.pack)
+        return pack(w, transposed, flip) if pack is not None else None
 
     def run(self, x, w, scale, shift, y, res=None, relu=None, w16=None, y16=None):
         """y16 (an RS16 tensor; transposed-conv plans on the LDS-free kernel only): the result is (also) written in the split-f16
         layout for a drc_conv3d_k3_s16_fwd consumer; y may then be None."""
-        p = self.p
-        if y16 is not None and not self.deconv_direct:
+        p, k = self.p, self.kernel
+        if y16 is not None and k.rs16 is None:
             raise ValueError("y16: only the LDS-free transposed convolution writes RS16")
-        if self.needs_t16:
-            points = (16 if self.c2d else 64) if self.wino else (9 if self.c2d else 27)
-            if w16 is None or w16.shape[1 if self.deconv_direct else 0] != points:
+        if k.points:
+            if w16 is None or w16.shape[k.axis] != k.points:
                 raise ValueError("this plan runs an LDS-free kernel: pass w16 = plan.pack16(weight)")
             w = w16
+        if (w.dim() == 3) != (k.pack == "pw"):
+            raise ValueError("weights are not in the packing this plan expects (engine.pack_conv_weight)")
         relu_saved = p.relu
         if relu is not None:
             p.relu = int(relu)
@@ -603,59 +602,24 @@ class ConvPlan:
             p.r_off0 = res.interior_off
         else:
             p.res = None
-        if TIMING is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(self.device))
-        if (w.dim() == 3) != self.pointwise:
-            raise ValueError("weights are not in the packing this plan expects (engine.pack_conv_weight)")
-        if self.wino and self.c2d and self.rb:
-            st = _lib.lib().drc_conv2d_k3_wino_rb_fwd(C.byref(p), _stream_ptr(self.device))
-            _lib.check(st, "drc_conv2d_k3_wino_rb_fwd")
-        elif self.wino and self.c2d:
-            st = _lib.lib().drc_conv2d_k3_wino_fwd(C.byref(p), self.slide_ct, _stream_ptr(self.device))
-            _lib.check(st, "drc_conv2d_k3_wino_fwd")
-        elif self.direct and self.c2d:
-            st = _lib.lib().drc_conv2d_k3_direct_fwd(C.byref(p), self.c2d_ct, _stream_ptr(self.device))
-            _lib.check(st, "drc_conv2d_k3_direct_fwd")
-        elif self.direct and self.down:
-            st = _lib.lib().drc_conv3d_k3s2_direct_fwd(C.byref(p), self.down_ct, _stream_ptr(self.device))
-            _lib.check(st, "drc_conv3d_k3s2_direct_fwd")
-        elif self.wino and self.rb:
-            st = _lib.lib().drc_conv3d_k3_wino_rb_fwd(C.byref(p), _stream_ptr(self.device))
-            _lib.check(st, "drc_conv3d_k3_wino_rb_fwd")
-        elif self.wino:
-            st = _lib.lib().drc_conv3d_k3_wino_fwd(C.byref(p), self.slide_ct, _stream_ptr(self.device))
-            _lib.check(st, "drc_conv3d_k3_wino_fwd")
-        elif self.direct and self.slide:
-            st = _lib.lib().drc_tapconv3d_direct_fwd(C.byref(p), self.slide_ct, _stream_ptr(self.device))
-            _lib.check(st, "drc_tapconv3d_direct_fwd")
-        elif self.pointwise:
-            st = _lib.lib().drc_conv2d_k1_fwd(C.byref(p), _stream_ptr(self.device))
-            _lib.check(st, "drc_conv2d_k1_fwd")
-        elif self.deconv_direct and y16 is not None:
-            st = _lib.lib().drc_deconv3d_k3s2_direct_s16_fwd(C.byref(p), _ptr(y16.storage), _ovf_ptr(), _stream_ptr(self.device))
-            _lib.check(st, "drc_deconv3d_k3s2_direct_s16_fwd")
-        elif self.deconv_direct:
-            st = _lib.lib().drc_deconv3d_k3s2_direct_fwd(C.byref(p), self.deconv_ct, _stream_ptr(self.device))
-            _lib.check(st, "drc_deconv3d_k3s2_direct_fwd")
-        elif self.fused_deconv:
-            st = _lib.lib().drc_deconv3d_k3s2_fwd(C.byref(p), _stream_ptr(self.device))
-            _lib.check(st, "drc_deconv3d_k3s2_fwd")
+        e0 = None if TIMING is None else _timing_start(self.device)
+        if y16 is not None:
+            entry, args = k.rs16, (_ptr(y16.storage), _ovf_ptr())
         else:
-            st = _lib.lib().drc_tapconv_fwd(C.byref(p), _stream_ptr(self.device))
-            _lib.check(st, "drc_tapconv_fwd")
+            entry, args = k.entry, self._ct_args
+        st = getattr(_lib.lib(), entry)(C.byref(p), *args, _stream_ptr(self.device))
+        _lib.check(st, entry)
         p.relu = relu_saved
-        if TIMING is not None:
-            e1.record(torch.cuda.current_stream(self.device))
-            TIMING.append((self.kname, self.flops, e0, e1))
-
+        if e0 is not None:
+            _timing_stop(e0, self.device, self.kname, self.flops)
 
     def run_costvol(self, left, right, lo4, w16, scale, shift, y):
         """dres0[0] straight from the feature maps (the cost volume is never materialised): `left`, `right` are blocked 2D feature
         tensors (D = 1, no depth halo, halo >= 1 in y and x) of the same geometry holding this plan's N maps each -- `right` may
         be a (Blocked, first_unit) pair naming a later range of the same tensor.  Only Winograd plans (plan.wino) have this form.
         Reference: stackhourglass.py:115-130."""
-        if not (self.wino and not self.c2d):
+        k = self.kernel
+        if k.costvol is None:
             raise ValueError("run_costvol needs a 3D Winograd plan")
         r_first = 0
         if isinstance(right, tuple):
@@ -668,7 +632,7 @@ class ConvPlan:
             raise ValueError("run_costvol: left and right feature maps differ in geometry")
         if left.N < p.N or right.N < r_first + p.N:
             raise ValueError("run_costvol: fewer feature maps than volume units")
-        if w16 is None or w16.shape[0] != 64:
+        if w16 is None or w16.shape[k.axis] != k.points:
             raise ValueError("run_costvol: pass w16 = plan.pack16(weight) (the plan's own packing: wino3d.hip's or wino3d_rb.hip's)")
         cv = _lib.DrcCostvolSrc()
         cv.left = _base_ptr(left)
@@ -681,18 +645,11 @@ class ConvPlan:
         p.y_off0 = y.interior_off
         p.w, p.scale, p.shift = w16.data_ptr(), scale.data_ptr(), shift.data_ptr()
         p.res = None
-        if TIMING is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(self.device))
-        if self.rb:
-            st = _lib.lib().drc_conv3d_k3_wino_rb_costvol_fwd(C.byref(p), C.byref(cv), _stream_ptr(self.device))
-            _lib.check(st, "drc_conv3d_k3_wino_rb_costvol_fwd")
-        else:
-            st = _lib.lib().drc_conv3d_k3_wino_costvol_fwd(C.byref(p), C.byref(cv), self.slide_ct, _stream_ptr(self.device))
-            _lib.check(st, "drc_conv3d_k3_wino_costvol_fwd")
-        if TIMING is not None:
-            e1.record(torch.cuda.current_stream(self.device))
-            TIMING.append((self.kname.replace("rb_kernel", "rb_cv_kernel") if self.rb else "wino3d_cv_kernel<%d>" % self.slide_ct, self.flops, e0, e1))
+        e0 = None if TIMING is None else _timing_start(self.device)
+        st = getattr(_lib.lib(), k.costvol)(C.byref(p), C.byref(cv), *self._ct_args, _stream_ptr(self.device))
+        _lib.check(st, k.costvol)
+        if e0 is not None:
+            _timing_stop(e0, self.device, self.kname.replace("_kernel", "_cv_kernel"), self.flops)
 
 
 # Kernel-selection switches (defaults = the fastest measured path; the tests flip them to keep every variant covered)
@@ -742,49 +699,48 @@ def plan_conv3d(x, y, stride, cout, relu):
     """Conv3d(k3,pad1,stride) on a blocked tensor with halo 1."""
     assert (x.pd, x.ph, x.pw) == (1, 1, 1)
     classes = taps_conv((3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1))
-    pl = ConvPlan(x, y, classes, stride, 1, (y.D, y.H, y.W), cout, relu, slide=(stride == 1 and SLIDE["enabled"]))
-    if pl.slide and DIRECT["enabled"]:
-        pl.direct = True
-        pl.kname = pl.kname.replace("tapslide", "tapdirect")
-        if WINO["enabled"] and not (y.D | y.H | y.W) & 1 and x.N * x.n_stride * 4 < 2 ** 32:
-            pl.wino = True
-            pl.kname = "wino3d_kernel<%d>" % pl.slide_ct
-            chunks = x.N * (y.D // 2) * (y.H // 2) * (y.W // 2) // 64
-            if (WINO.get("rb") and chunks * (pl.p.cout_pad // 32) >= WINO["rb_min_chunks"]
-                    and _lib.lib().drc_conv3d_k3_wino_rb_supported(pl.p.cout_pad, y.D, y.H, y.W)):
-                pl.rb = True
-                pl.kname = "wino3d_rb_kernel<%d>" % (7 if y.W == 14 else 14)
-    elif not pl.slide and stride == 1 and SLIDE["enabled"] and DIRECT["enabled"] and getattr(pl, "slide_small_ok", False):
-        wchunks = x.N * (y.D // 2) * (y.H // 2) * (y.W // 2) // 64
-        if WINO["enabled"] and wchunks >= WINO["small"] > 0 and not (y.D | y.H | y.W) & 1 and x.N * x.n_stride * 4 < 2 ** 32:
-            # even maps at small batch (Config B's quarter-resolution hourglass layers, 16 ROIs: 6 x 14 x 14): Winograd still halves
-            # the generic kernel's time (4 ROIs at 12 x 28 x 28: 74 vs 119 us direct; round 3 -- rounds 1-2 sent these to tapconv);
-            # below ~48 chunks every kernel sits at its ~65 us latency floor and the direct one is marginally ahead
-            pl.slide, pl.direct, pl.wino = True, True, True
-            pl.slide_ct = SLIDE["ct"] if (pl.p.cout_pad // 16) % SLIDE["ct"] == 0 else 1
-            pl.kname = "wino3d_kernel<%d>" % pl.slide_ct
-        else:
-            # odd maps (no Winograd) at small batch: the direct kernel with one cout tile per wave
-            pl.slide, pl.direct, pl.slide_ct = True, True, 1
-            pl.kname = "tapdirect_kernel<%d,1>" % (-(-(pl.p.R * pl.p.WT) // 16))
-    elif pl.slide:
-        # DIRECT off: the generic kernel (tapconv.hip).  (Rounds 1-2 had an LDS-staged sliding-window kernel here -- tapslide.hip -- which no
-        # default plan selected any more; it left the library in round 6, attic/.)
-        pl.slide = False
-        pl.kname = pl._generic_kname
+    OD, OH, OW = grid = (y.D, y.H, y.W)
+    slide = stride == 1 and SLIDE["enabled"]
+    R, WT, lds, kname = tapconv_choice(x, classes, stride, grid, cout, SLIDE["max_slots"] if slide else MAX_SLOTS)
+    kernel, ct = KERNELS["tapconv"], None           # (the generic kernel: DIRECT off, a handful of voxels, stride 2 with DOWN off)
+    nvt = -(-(R * WT) // 16)
+    tiles = cout_pad_of(cout) // 16
+    if slide and DIRECT["enabled"]:
+        # the sliding-window kernels give every resident wave an equal share (>= 3 output slices) of the (cout group, column, slice) units:
+        # used with SLIDE["ct"] cout tiles per wave only when that still yields enough waves to fill the 1024 SIMDs (measured cross-over,
+        # tools/experiments/exp_conv.py)
+        slide_ct = SLIDE["ct"] if tiles % SLIDE["ct"] == 0 else 1
+        cols = x.N * (-(-OH // R)) * (-(-OW // WT))
+        even = not (OD | OH | OW) & 1 and x.N * x.n_stride * 4 < 2 ** 32        # what the Winograd kernels take
+        chunks = x.N * (OD // 2) * (OH // 2) * (OW // 2) // 64
+        if OD >= SLIDE["min_od"] and cols * (tiles // slide_ct) * OD // SLIDE["min_share"] >= SLIDE["min_units"]:
+            kernel, ct, kname = KERNELS["tapdirect"], slide_ct, "tapdirect_kernel<%d,%d>" % (nvt, slide_ct)
+            if WINO["enabled"] and even:
+                kernel, kname = KERNELS["wino3d"], "wino3d_kernel<%d>" % slide_ct
+                if (WINO.get("rb") and chunks * (cout_pad_of(cout) // 32) >= WINO["rb_min_chunks"]
+                        and _lib.lib().drc_conv3d_k3_wino_rb_supported(cout_pad_of(cout), OD, OH, OW)):
+                    kernel, ct, kname = KERNELS["wino3d_rb"], None, "wino3d_rb_kernel<%d>" % (7 if OW == 14 else 14)
+        elif OD >= SLIDE["min_od"] and cols * tiles * OD >= SLIDE["min_units_ct1"]:
+            # small batches: with ONE cout tile per wave the LDS-free direct kernel still beats the generic kernel down to ~150 units
+            # (3x7x7 maps, 64->64: 47 vs 87 us at 64 ROIs, 45 vs 84 us at 16; at 128 ROIs two tiles per wave win, 75 vs 93 us)
+            if WINO["enabled"] and chunks >= WINO["small"] > 0 and even:
+                # even maps at small batch (Config B's quarter-resolution hourglass layers, 16 ROIs: 6 x 14 x 14): Winograd still halves
+                # the generic kernel's time (4 ROIs at 12 x 28 x 28: 74 vs 119 us direct; round 3 -- rounds 1-2 sent these to tapconv);
+                # below ~48 chunks every kernel sits at its ~65 us latency floor and the direct one is marginally ahead
+                kernel, ct, kname = KERNELS["wino3d"], slide_ct, "wino3d_kernel<%d>" % slide_ct
+            else:
+                # odd maps (no Winograd) at small batch: the direct kernel with one cout tile per wave
+                kernel, ct, kname = KERNELS["tapdirect"], 1, "tapdirect_kernel<%d,1>" % nvt
     if stride == 2 and DOWN["enabled"] and DIRECT["enabled"] and DIRECT.get("down", True):      # (else: the generic kernel)
-        pl.down = True
-        pl.p.R, pl.p.WT = choose_tile_down(y.H, y.W)
-        nvt = -(-(pl.p.R * pl.p.WT) // 16)
-        ct = pl.p.cout_pad // 16
-        tiles = x.N * y.D * (-(-y.H // pl.p.R)) * (-(-y.W // pl.p.WT))
-        CT = 4 if ct % 4 == 0 else (2 if ct % 2 == 0 else 1)
-        while CT > 1 and (nvt * CT > 28 or tiles * (ct // CT) < DOWN["min_groups"]):
-            CT //= 2
-        pl.down_ct = CT
-        pl.direct = True
-        pl.kname = "downdirect_kernel<%d,%d>" % (nvt, CT)
-    return pl
+        R, WT = choose_tile_down(OH, OW)
+        nvt = -(-(R * WT) // 16)
+        ntile = x.N * OD * (-(-OH // R)) * (-(-OW // WT))
+        ct = 4 if tiles % 4 == 0 else (2 if tiles % 2 == 0 else 1)
+        while ct > 1 and (nvt * ct > 28 or ntile * (tiles // ct) < DOWN["min_groups"]):
+            ct //= 2
+        kernel, kname = KERNELS["downdirect"], "downdirect_kernel<%d,%d>" % (nvt, ct)
+    return ConvPlan(x, y, classes, stride, 1, grid, cout, relu, kernel, kname, (R, WT), lds, ct)
+
 
 
 FUSED_DECONV = {"enabled": True}
@@ -816,91 +772,86 @@ def choose_tile_deconv(H, W):
 
 def plan_deconv3d(x, y, cout, relu):
     assert (x.pd, x.ph, x.pw) == (1, 1, 1) and (y.D, y.H, y.W) == (2 * x.D, 2 * x.H, 2 * x.W)
-    pl = ConvPlan(x, y, taps_deconv3d_k3s2(), 1, 2, (x.D, x.H, x.W), cout, relu)
+    classes, grid = taps_deconv3d_k3s2(), (x.D, x.H, x.W)
+    R, WT, lds, kname = tapconv_choice(x, classes, 1, grid, cout)
+    kernel, ct = KERNELS["tapconv"], None
+    tiles = cout_pad_of(cout) // 16
     if FUSED_DECONV["enabled"]:
-        pl.fused_deconv = True
-        pl.p.R, pl.p.WT = choose_tile_deconv(x.H, x.W)
-        nvt = -(-(pl.p.R * pl.p.WT) // 16)
-        pl.kname = "tapdeconv_kernel<%d,%d>" % (nvt, 2 if nvt <= 3 and (pl.p.cout_pad // 16) % 2 == 0 else 1)
+        R, WT = choose_tile_deconv(x.H, x.W)
+        nvt = -(-(R * WT) // 16)
+        kernel, kname = KERNELS["tapdeconv"], "tapdeconv_kernel<%d,%d>" % (nvt, 2 if nvt <= 3 and tiles % 2 == 0 else 1)
         if (DIRECT["enabled"] and DECONV_DIRECT["enabled"] and x.N * x.n_stride * 4 < 2 ** 32 and y.N * y.n_stride * 4 < 2 ** 32):
             # LDS-free kernel: 32 consecutive voxels of the flattened (n,d,h,w) index per wave (no tile shape), two cout tiles per wave
             # when the cout tiles pair up (every layer of the regressor)
-            ct = pl.p.cout_pad // 16
-            CT = 2 if ct % 2 == 0 and DECONV_DIRECT["ct"] == 2 else 1
-            pl.deconv_direct, pl.direct, pl.deconv_ct = True, True, CT
-            pl.p.R, pl.p.WT = 1, min(x.W, 32)
-            pl.kname = "deconvdirect_kernel<2,%d>" % CT
-    return pl
+            ct = 2 if tiles % 2 == 0 and DECONV_DIRECT["ct"] == 2 else 1
+            R, WT = 1, min(x.W, 32)
+            kernel, kname = KERNELS["deconvdirect"], "deconvdirect_kernel<2,%d>" % ct
+    return ConvPlan(x, y, classes, 1, 2, grid, cout, relu, kernel, kname, (R, WT), lds, ct)
 
 
 def plan_conv2d(x, y, k, stride, pad, dilation, cout, relu):
     """Conv2d(k,stride,pad,dilation) on blocked 2D tensors (D=1, pd=0)."""
     assert x.pd == 0 and x.D == 1
-    classes = taps_conv((1, k, k), (1, dilation, dilation), (0, pad, pad), (0, x.ph, x.pw))
-    pl = ConvPlan(x, y, classes, stride, 1, (1, y.H, y.W), cout, relu)
+    classes, grid = taps_conv((1, k, k), (1, dilation, dilation), (0, pad, pad), (0, x.ph, x.pw)), (1, y.H, y.W)
+    R, WT, lds, kname = tapconv_choice(x, classes, stride, grid, cout)
+    kernel, ct = KERNELS["tapconv"], None
+    tiles = cout_pad_of(cout) // 16
     if k == 3 and DIRECT["enabled"] and DIRECT.get("conv2d", True):
         # LDS-free kernel: any stride (1|2) and dilation; the tile only has to give full voxel tiles
         best = None
-        ct_ = pl.p.cout_pad // 16
         for r in range(1, min(y.H, MAX_SLOTS) + 1):
             for wt in range(1, min(y.W, MAX_SLOTS // r) + 1):
-                nvt_ = -(-(r * wt) // 16)
+                nvt = -(-(r * wt) // 16)
                 ntile = x.N * (-(-y.H // r)) * (-(-y.W // wt))
-                waste = (-(-y.H // r)) * (-(-y.W // wt)) * nvt_ * 16 / (y.H * y.W)
+                waste = (-(-y.H // r)) * (-(-y.W // wt)) * nvt * 16 / (y.H * y.W)
                 # small maps with many channels (the trunk's 512 -> 512 layers on 12 x 39: 12 whole-row tiles x 32 cout tiles = 384 waves for
                 # 1024 SIMDs, each walking K = 4608): a smaller tile that fills the chip beats the one with the least padding (round 3)
-                fill = min(1.0, ntile * ct_ / 1024.0) if CONV2D_FILL["enabled"] else 1.0
+                fill = min(1.0, ntile * tiles / 1024.0) if CONV2D_FILL["enabled"] else 1.0
                 key = (round(fill / waste, 2), r * wt, wt)
                 if best is None or key > best[0]:
                     best = (key, r, wt)
-        pl.c2d, pl.direct = True, True
-        pl.p.R, pl.p.WT = best[1], best[2]
-        nvt = -(-(best[1] * best[2]) // 16)
-        ct = pl.p.cout_pad // 16
-        tiles = x.N * (-(-y.H // best[1])) * (-(-y.W // best[2]))
-        CT = 4 if ct % 4 == 0 else (2 if ct % 2 == 0 else 1)
-        while CT > 1 and (nvt * CT > 28 or tiles * (ct // CT) < 700):
-            CT //= 2
-        pl.c2d_ct = CT
-        pl.kname = "conv2ddirect_kernel<%d,%d>" % (nvt, CT)
+        R, WT = best[1], best[2]
+        nvt = -(-(R * WT) // 16)
+        ntile = x.N * (-(-y.H // R)) * (-(-y.W // WT))
+        ct = 4 if tiles % 4 == 0 else (2 if tiles % 2 == 0 else 1)
+        while ct > 1 and (nvt * ct > 28 or ntile * (tiles // ct) < 700):
+            ct //= 2
+        kernel, kname = KERNELS["conv2ddirect"], "conv2ddirect_kernel<%d,%d>" % (nvt, ct)
         # stride-1, undilated layers on even maps with enough tile groups for every block: Winograd F(2x2,3x3) (wino2d.hip)
-        wct = 2 if ct % 2 == 0 else 1
         # (odd maps: the last tile row / column is half used, wino2d.hip; their patch row 3 lies in the slack behind the tensor)
         wtiles = x.N * ((y.H + 1) // 2) * ((y.W + 1) // 2)
         # (drc_conv2d_k3_wino_fwd instantiates dilations 1, 2 and 4 only; any other 3x3 layer keeps the direct kernel)
         dil_ok = dilation == 1 or (WINO2D["dilated"] and dilation in (2, 4) and y.H % (2 * dilation) == 0 and y.W % (2 * dilation) == 0)
         if (WINO2D["enabled"] and stride == 1 and dil_ok and pad == dilation and (WINO2D["odd"] or not (y.H | y.W) & 1) and
                 (x.N * x.n_stride + 2 * x.h_stride) * 4 < 2 ** 32 and wtiles // 64 >= WINO2D["min_chunks"]):
-            pl.wino = True
-            pl.slide_ct = wct
-            pl.kname = "wino2d_kernel<%d>" % wct
-            chunks = wtiles // 64
-            if (WINO2D.get("rb") and dilation == 1 and x.cb <= WINO2D["rb_max_cb"] and not (y.H | y.W) & 1 and chunks * (pl.p.cout_pad // 32) >= WINO2D["rb_min_chunks"]
-                    and _lib.lib().drc_conv2d_k3_wino_rb_supported(pl.p.cout_pad, y.H, y.W)):
-                pl.rb = True
-                pl.kname = "wino2d_rb_kernel<%d>" % (7 if y.W == 14 else 14)
+            ct = 2 if tiles % 2 == 0 else 1
+            kernel, kname = KERNELS["wino2d"], "wino2d_kernel<%d>" % ct
+            if (WINO2D.get("rb") and dilation == 1 and x.cb <= WINO2D["rb_max_cb"] and not (y.H | y.W) & 1 and wtiles // 64 * (cout_pad_of(cout) // 32) >= WINO2D["rb_min_chunks"]
+                    and _lib.lib().drc_conv2d_k3_wino_rb_supported(cout_pad_of(cout), y.H, y.W)):
+                kernel, ct, kname = KERNELS["wino2d_rb"], None, "wino2d_rb_kernel<%d>" % (7 if y.W == 14 else 14)
     if k == 1 and POINTWISE["enabled"]:
-        pl.pointwise = True
-        ct = pl.p.cout_pad // 16
-        tiles = -(-(x.N * y.H * y.W) // 16)
-        if ct % 4 == 0 and tiles // 4 * (ct // 4) >= 2048:
+        ntile = -(-(x.N * y.H * y.W) // 16)
+        if tiles % 4 == 0 and ntile // 4 * (tiles // 4) >= 2048:
             vc = (4, 4)
-        elif ct % 2 == 0 and tiles // 4 * (ct // 2) >= 2048:
+        elif tiles % 2 == 0 and ntile // 4 * (tiles // 2) >= 2048:
             vc = (4, 2)
-        elif ct % 2 == 0 and (tiles // 2 * (ct // 2) >= 1024 or x.cb < 16):        # mirrors drc_conv2d_k1_fwd's choice
+        elif tiles % 2 == 0 and (ntile // 2 * (tiles // 2) >= 1024 or x.cb < 16):        # mirrors drc_conv2d_k1_fwd's choice
             vc = (2, 2)
-        elif tiles // 2 * ct >= 1024:
+        elif ntile // 2 * tiles >= 1024:
             vc = (2, 1)
         else:
             vc = (1, 1)
-        pl.kname = "pointwise_kernel<%d,%d>" % vc
-    return pl
+        kernel, kname = KERNELS["pointwise"], "pointwise_kernel<%d,%d>" % vc
+    return ConvPlan(x, y, classes, stride, 1, grid, cout, relu, kernel, kname, (R, WT), lds, ct)
 
 
 def plan_deconv2d(x, y, k, cout, relu=False):
     """2D transposed conv (k in {1,3}, stride 2) on blocked tensors: y is exactly twice x."""
     assert x.pd == 0 and x.D == 1 and (y.H, y.W) == (2 * x.H, 2 * x.W) and x.ph >= 1 and x.pw >= 1
-    return ConvPlan(x, y, taps_deconv2d_s2(k, (0, x.ph, x.pw)), 1, 2, (1, x.H, x.W), cout, relu)
+    classes, grid = taps_deconv2d_s2(k, (0, x.ph, x.pw)), (1, x.H, x.W)
+    R, WT, lds, kname = tapconv_choice(x, classes, 1, grid, cout)
+    return ConvPlan(x, y, classes, 1, 2, grid, cout, relu, KERNELS["tapconv"], kname, (R, WT), lds)
+
 
 
 # ------------------------------------------------------------------------------------------- other ops
@@ -1247,7 +1198,7 @@ class ConvPlan16:
     """A resolved conv16 launch (tap-grid classes as in ConvPlan).  dense1: the 32 -> 1 classifier conv, whose single cout is
     written as a dense fp32 [N,D,H,W] volume (+ an optional dense fp32 residual)."""
 
-    def __init__(self, x, y_geom, classes, in_mul, out_mul, grid_dhw, cout, relu, dense1=False):
+    def __init__(self, x, y_geom, classes, in_mul, out_mul, grid_dhw, cout, relu, dense1=False, costvol_lo4=None):
         p = DrcTapconvParams()
         OD, OH, OW = grid_dhw
         p.N, p.OD, p.OH, p.OW = x.N, OD, OH, OW
@@ -1255,46 +1206,52 @@ class ConvPlan16:
         p.cb_in = x.cb
         p.cout_pad = (cout + CB - 1) // CB * CB
         p.relu = int(relu)
-        p.n_classes = len(classes)
         p.R, p.WT = choose_tile16(OH, OW)
         p.reserved = 1 if dense1 else 0
-        for ci, c in enumerate(classes):
-            k = p.cls[ci]
-            k.nd, k.nh, k.nw = c["n"]
-            k.dd0, k.dh0, k.dw0 = c["first"]
-            k.sd, k.sh, k.sw = c["step"]
-            k.wbase = c["wbase"]
-            k.wsd, k.wsh, k.wsw = c["wstep"]
-            k.out_off_d, k.out_off_h, k.out_off_w = c["off"]
+        ntaps = fill_tap_classes(p, classes)
         self.p, self.device, self.dense1 = p, x.device, dense1
-        ntaps = sum(c["n"][0] * c["n"][1] * c["n"][2] for c in classes)
         self.flops = 2 * x.N * OD * OH * OW * ntaps * x.C * cout
-        self.kname = "conv16_kernel<%d,%d>" % (min(-(-(p.R * p.WT) // 16), 4), 2 if (p.cout_pad // 16) % 2 == 0 else 1)
-        self.tile = bool(C16_TILE["enabled"] and _lib.lib().drc_conv16_k3_tile_supported(C.byref(p)))
+        # plan_conv3d16_costvol: x is the feature pair, the cost volume is folded into the stage addresses; the volume's first disparity is the
+        # entry's extra argument (PSMNetRuntime sets it per forward)
+        self.costvol_lo4 = costvol_lo4
         ct = p.cout_pad // 16
         cw = 4 if ct % 4 == 0 else (2 if ct % 2 == 0 else 1)                       # cout tiles side by side in a block of conv16x.hip
-        if self.tile:
+        kd = classes[0]["n"][0]
+        self.entry = "drc_conv16_fwd"                                               # conv16.hip's generic tap walk
+        self.kname = "conv16_kernel<%d,%d>" % (min(-(-(p.R * p.WT) // 16), 4), 2 if ct % 2 == 0 else 1)
+        if costvol_lo4 is not None:
+            self.entry = "drc_conv16_k3_costvol_fwd"
+            self.kname = "conv16sw_kernel<7,%d,cv>" % cw if walk2_takes(2, OD, OH, cw) else "conv16d_kernel<%d,%d,1,cv>" % (x16_rows(OH, cw, 1), cw)
+        elif C16_TILE["enabled"] and _lib.lib().drc_conv16_k3_tile_supported(C.byref(p)):
+            self.entry = "drc_conv16_k3_tile_fwd"
             rw = 4 if (OH % 16 == 0 or OH >= 48) else 2
-            if classes[0]["n"][0] == 3 and x.cb == 1 and p.cout_pad <= 32 and OD >= 4:      # conv16t.hip: the depth-sliding walk
+            if kd == 3 and x.cb == 1 and p.cout_pad <= 32 and OD >= 4:                      # conv16t.hip: the depth-sliding walk
                 self.kname = "conv16s_kernel<%d,%d>" % (rw, ct)
                 if OH % 28 == 0 or OH % 16 == 0:                                            # rows fill the tiles: two slices in flight (round 4)
                     self.kname = "conv16sp_kernel<%d,%d>" % (7 if OH % 28 == 0 else 4, ct)
-            elif classes[0]["n"][0] == 3 and not dense1:                                     # conv16x.hip, stride 1 (round 4)
+            elif kd == 3 and not dense1:                                                    # conv16x.hip, stride 1 (round 4)
                 self.kname = "conv16d_kernel<%d,%d,1>" % (x16_rows(OH, cw, 1), cw)
                 if walk2_takes(x.cb, OD, OH, cw):                                            # two input blocks, full row tiles: the depth walk
                     self.kname = "conv16sw_kernel<7,%d>" % cw
             else:
-                self.kname = "conv16t_kernel<%d,%d,%d>" % (rw, cw, classes[0]["n"][0])
-        self.costvol_lo4 = None          # plan_conv3d16_costvol: x is the feature pair, the cost volume is folded into the stage addresses
+                self.kname = "conv16t_kernel<%d,%d,%d>" % (rw, cw, kd)
         # round 4 (conv16x.hip): the stride-2 and transposed 3x3x3 layers on LDS tiles too
-        self.tile_x = None
-        if C16_TILE["enabled"] and not self.tile and not dense1:
-            if _lib.lib().drc_conv16_k3s2_tile_supported(C.byref(p)):
-                self.tile_x = "drc_conv16_k3s2_tile_fwd"
-                self.kname = "conv16d_kernel<%d,%d,2>" % (x16_rows(OH, cw, 2), cw)
-            elif _lib.lib().drc_deconv16_k3s2_tile_supported(C.byref(p)):
-                self.tile_x = "drc_deconv16_k3s2_tile_fwd"
-                self.kname = "conv16u_kernel<%d,%d,%d>" % (x16_rows(OH, cw, 0, x.cb), cw, x.cb)
+        elif C16_TILE["enabled"] and not dense1 and _lib.lib().drc_conv16_k3s2_tile_supported(C.byref(p)):
+            self.entry = "drc_conv16_k3s2_tile_fwd"
+            self.kname = "conv16d_kernel<%d,%d,2>" % (x16_rows(OH, cw, 2), cw)
+        elif C16_TILE["enabled"] and not dense1 and _lib.lib().drc_deconv16_k3s2_tile_supported(C.byref(p)):
+            self.entry = "drc_deconv16_k3s2_tile_fwd"
+            self.kname = "conv16u_kernel<%d,%d,%d>" % (x16_rows(OH, cw, 0, x.cb), cw, x.cb)
+
+    @property
+    def tile(self):
+        """True on conv16t.hip's / conv16x.hip's stride-1 LDS-tiled entry."""
+        return self.entry == "drc_conv16_k3_tile_fwd"
+
+    @property
+    def tile_x(self):
+        """The entry of conv16x.hip's stride-2 / transposed LDS-tiled kernels when the plan runs one, else None."""
+        return self.entry if self.entry in ("drc_conv16_k3s2_tile_fwd", "drc_deconv16_k3s2_tile_fwd") else None
 
     def run(self, x, w16, scale, shift, y, res=None):
         p = self.p
@@ -1315,24 +1272,12 @@ class ConvPlan16:
                 p.r_off0 = res.interior_off
             else:
                 p.res = None
-        if TIMING is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(self.device))
-        if self.costvol_lo4 is not None:
-            st = _lib.lib().drc_conv16_k3_costvol_fwd(C.byref(p), self.costvol_lo4, _stream_ptr(self.device))
-            _lib.check(st, "drc_conv16_k3_costvol_fwd")
-        elif self.tile:
-            st = _lib.lib().drc_conv16_k3_tile_fwd(C.byref(p), _stream_ptr(self.device))
-            _lib.check(st, "drc_conv16_k3_tile_fwd")
-        elif self.tile_x:
-            st = getattr(_lib.lib(), self.tile_x)(C.byref(p), _stream_ptr(self.device))
-            _lib.check(st, self.tile_x)
-        else:
-            st = _lib.lib().drc_conv16_fwd(C.byref(p), _stream_ptr(self.device))
-            _lib.check(st, "drc_conv16_fwd")
-        if TIMING is not None:
-            e1.record(torch.cuda.current_stream(self.device))
-            TIMING.append((self.kname, self.flops, e0, e1))
+        e0 = None if TIMING is None else _timing_start(self.device)
+        args = () if self.costvol_lo4 is None else (self.costvol_lo4,)
+        st = getattr(_lib.lib(), self.entry)(C.byref(p), *args, _stream_ptr(self.device))
+        _lib.check(st, self.entry)
+        if e0 is not None:
+            _timing_stop(e0, self.device, self.kname, self.flops)
 
 
 def plan_conv3d16(x, y, stride, cout, relu):
@@ -1348,15 +1293,7 @@ def plan_conv3d16_costvol(pair, y, lo4, cout, relu):
     [N,64,1,H,W] (channel block 0 = left features, block 1 = right features; cost_volume16_blocked / cost_volume16_from16 with one slice at
     disparity 0), y = Blocked16 [N,cout,D,H,W], lo4 = the volume's first disparity.  Bit-identical to the two-kernel form."""
     assert (pair.pd, pair.ph, pair.pw) == (1, 1, 1) and pair.C == 64 and pair.D == 1 and (pair.H, pair.W) == (y.H, y.W)
-    pl = ConvPlan16(pair, y, taps_conv((3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1)), 1, 1, (y.D, y.H, y.W), cout, relu)
-    pl.costvol_lo4, pl.tile, pl.tile_x = int(lo4), False, None
-    ct = pl.p.cout_pad // 16
-    cw = 4 if ct % 4 == 0 else (2 if ct % 2 == 0 else 1)
-    pl.kname = "conv16d_kernel<%d,%d,1,cv>" % (x16_rows(y.H, cw, 1), cw)
-    if walk2_takes(2, y.D, y.H, cw):
-        pl.kname = "conv16sw_kernel<7,%d,cv>" % cw
-    pl.flops = 2 * y.N * y.D * y.H * y.W * 27 * 64 * cout
-    return pl
+    return ConvPlan16(pair, y, taps_conv((3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1)), 1, 1, (y.D, y.H, y.W), cout, relu, costvol_lo4=int(lo4))
 
 
 def plan_deconv3d16(x, y, cout, relu):
@@ -1689,14 +1626,11 @@ class ConvPlanS16:
                              0x800 if (self.cv and self.kind == "s1" and not CV_WIDE["enabled"]) else int(self.dil) | self._flat_bits(),   # (the library's switch bits of the 3D layers' unused `dil` field: keep the one-row kernel; row / flat tiles)
                              _ptr(head[1]) if head is not None else None, _ptr(head[0]) if head is not None else None, _ovf_ptr(), int(bool(head_rows)))
         dev = self.device
-        if TIMING is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(dev))
+        e0 = None if TIMING is None else _timing_start(dev)
         fn = {"s1": "drc_conv3d_k3_s16_fwd", "s2": "drc_conv3d_k3s2_s16_fwd", "up": "drc_deconv3d_k3s2_s16_fwd", "2d": "drc_conv2d_k3_s16_fwd"}[self.kind]
         st = getattr(_lib.lib(), fn)(C.byref(p), _stream_ptr(dev))
         _lib.check(st, fn)
-        if TIMING is not None:
-            e1.record(torch.cuda.current_stream(dev))
+        if e0 is not None:
             if self.kind == "s1" and self._wide and res is None and y32 is None and head is None:
                 kn = self._wname
             elif self.kind == "s1":
@@ -1706,4 +1640,4 @@ class ConvPlanS16:
             else:
                 kn = self.kname
             # (a fused-head launch also computes the 32 -> 1 layer behind it: 2 * 27 * 32 flops per voxel on top of the layer's own)
-            TIMING.append((kn, self.flops + (2 * 27 * 32 * self.N * self.D * self.H * self.W if head is not None else 0), e0, e1))
+            _timing_stop(e0, dev, kn, self.flops + (2 * 27 * 32 * self.N * self.D * self.H * self.W if head is not None else 0))

@@ -134,20 +134,15 @@ class RegressorBackward:
             cache[plan_name] = ent
         # transformed weights, both packings from one launch (drc_pack_weights: in/out swap and tap flip are index arithmetic)
         pl = ent["plan"]
-        need16 = pl.needs_t16
-        if deconv:                      # ConvTranspose weight [Cin,Cout,k] read as Conv[out=Cin, in=Cout]
-            wp, w16 = E.pack_layouts(wt, False, False, want_t16=need16)
-        elif stride == 2:               # Conv weight [Cout,Cin,k] as the transposed conv's [in=Cout, out=Cin]
-            if pl.deconv_direct:
-                wp, w16 = E.pack_layouts(wt, True, False, want_t16=False)[0], pl.pack16(wt, True, False)
-            else:
-                wp, w16 = E.pack_layouts(wt, True, False, want_t16=need16)
-        elif pl.pointwise:              # 1x1: in/out swap only
-            wp, w16 = E.pack_layouts(wt, True, False, want_tap=False)[1][0], None
-        elif pl.wino:                   # stride 1 as Winograd: in/out swap + flipped taps inside the weight transform
-            wp, w16 = E.pack_layouts(wt, True, True, want_t16=False)[0], pl.pack16(wt, True, True)
-        else:                           # stride 1: in/out swap + flipped taps
-            wp, w16 = E.pack_layouts(wt, True, True, want_t16=need16)
+        # ConvTranspose weight [Cin,Cout,k]: read as Conv[out=Cin, in=Cout]; Conv weight [Cout,Cin,k]: in/out swap (stride 2: as the transposed
+        # conv's [in=Cout, out=Cin]), at stride 1 with flipped taps (a 1x1 kernel has none to flip)
+        swap, flip = not deconv, not deconv and stride != 2 and not pl.pointwise
+        if pl.pointwise and not deconv:
+            wp, w16 = E.pack_layouts(wt, swap, flip, want_tap=False)[1][0], None
+        elif pl.pack_kind in ("tap", "t16"):
+            wp, w16 = E.pack_layouts(wt, swap, flip, want_t16=pl.needs_t16)
+        else:                           # a packing of the plan's own (Winograd, deconvdirect.hip): the swap and flip go into its transform
+            wp, w16 = E.pack_layouts(wt, swap, flip, want_t16=False)[0], pl.pack16(wt, swap, flip)
         cp = ent["plan"].p.cout_pad
         unit = self.ws.setdefault("unit_affine", {})
         if cp not in unit:

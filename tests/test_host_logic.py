@@ -547,3 +547,49 @@ def test_roofline_traffic_is_tied_to_the_kernel_sources():
     assert meta.get("csrc_sha") and len(meta.get("commit", "")) >= 7
     assert meta["csrc_sha"] == source_digest(), "kernel sources changed since profiles/r6_* were collected: re-run profiles/collect_all.sh r6"
 
+
+def test_plans_match_the_committed_dump():
+    """Which kernel, tile, cout tiles, parameter block and C entry the engine plans for every layer of tools/dump_plans.py's sweep -- all batch
+    sizes, default switches and each switch off -- is what tests/golden/plans_golden.json records: per case the default kernel's name and a
+    digest of the case's line of the full dump (taken from the if-chain dispatch that preceded the kernel records; regenerate it with the tool
+    only for a deliberate change of a kernel choice).  The tool itself fails when a plan's kernel record and its flag properties name
+    different entries."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("dump_plans", os.path.join(ROOT, "tools", "dump_plans.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    full = mod.dump_lines()
+    got = mod.golden_lines(full)
+    want = open(os.path.join(ROOT, "tests", "golden", "plans_golden.json")).read().splitlines()
+    assert len(got) == len(want)
+    for g, w, line in zip(got, want, full):
+        assert g == w, line
+
+
+def test_kernel_table_and_read_only_flags():
+    """Every fp32 plan carries one record of engine.KERNELS; its flags are read-only views of that record and a plan is not edited after
+    plan_* returned it.  The GPU tests that launch each row (tests/test_hip_parity.py unless named): tapconv
+    test_generic_kernel_variants_vs_oracle; tapdirect test_conv3d_direct_kernel_vs_oracle, and test_conv3d_layer_vs_oracle's 12x28x28 case
+    for the small-batch one-cout-tile form; wino3d test_conv3d_winograd_kernel_vs_oracle; wino3d_rb test_conv3d_winograd_rowbrick_kernel;
+    their cost-volume entries test_conv3d_winograd_fused_cost_volume (n = 19: the row-brick one); downdirect and deconvdirect
+    test_conv3d_layer_vs_oracle's stride-2 / transposed cases; deconvdirect's RS16 entry
+    test_hip_s16.py::test_deconv_direct_writes_rs16_identical_to_its_fp32_output; tapdeconv test_deconv_lds_staged_variant_vs_oracle;
+    conv2ddirect and pointwise test_conv2d_layer_vs_oracle; wino2d test_conv2d_winograd_kernel_vs_oracle; wino2d_rb
+    test_conv2d_winograd_rowbrick_kernel.  ConvPlan16's entries (tests/test_hip_f16.py): the stride-1 / stride-2 / transposed tiles
+    test_conv16_layer_vs_fp32_conv_of_rounded_operands, the cost-volume entry test_costvol_fused_first_layer_is_bit_identical, conv16.hip's
+    generic walk test_f16_feature_cnn_vs_fp32_path (the 2D stride-2 and 1x1 layers)."""
+    from disprcnn_amd import engine as E
+    assert sorted(E.KERNELS) == sorted(["tapconv", "tapdirect", "wino3d", "wino3d_rb", "downdirect", "tapdeconv", "deconvdirect", "conv2ddirect",
+                                        "wino2d", "wino2d_rb", "pointwise"])
+    assert {k.pack for k in E.KERNELS.values()} == {"tap", "t16", "wino", "wino_rb", "wino2d", "wino2d_rb", "deconv_direct", "pw"}
+    assert [n for n, k in E.KERNELS.items() if k.costvol] == ["wino3d", "wino3d_rb"] and [n for n, k in E.KERNELS.items() if k.rs16] == ["deconvdirect"]
+    dev = torch.device("cpu")
+    g = E.Blocked.geometry(256, 32, 12, 28, 28, 1, 1, 1, dev)
+    pl = E.plan_conv3d(g, g, 1, 32, True)
+    assert pl.kernel is E.KERNELS["wino3d_rb"] and pl.wino and pl.rb and pl.needs_t16 and pl.pack_kind == "wino_rb"
+    for flag in ("slide", "fused_deconv", "down", "pointwise", "direct", "wino", "rb", "c2d", "deconv_direct", "needs_t16", "pack_kind"):
+        with pytest.raises(AttributeError):
+            setattr(pl, flag, False)
+    with pytest.raises(AttributeError):
+        pl.kernel.entry = "drc_tapconv_fwd"
+
