@@ -1,8 +1,8 @@
 """BoxCoder -- drop-in for ``disprcnn.modeling.box_coder.BoxCoder`` (box_coder.py:6-279).
 
 ``decode`` runs in libdisprcnn_hip.so (drc_box_decode_fwd): 4 codes per class (x1y1x2y2) or 6 (x1y1x2y2 + x1', x2' of the right view,
-decoded against 4-coordinate reference boxes -- the form the Stereo RPN and the stereo box head use).  ``encode`` (training targets of
-the 2D stage, which is not trained here) is plain tensor arithmetic."""
+decoded against 4-coordinate reference boxes -- the form the Stereo RPN and the stereo box head use).  ``encode`` is plain tensor arithmetic: the 2D
+stage's training targets are coded inside the matching kernel (layers/det2d_loss.py), and this is its comparator."""
 import math
 
 import torch
@@ -42,7 +42,8 @@ class BoxCoder:
         return out
 
     def encode(self, reference_boxes, proposals):
-        """Targets (dx, dy, dw, dh[, dx', dw']) of reference boxes [R,4|6] w.r.t. proposals [R,4] (box_coder.py:21-50,83-116)."""
+        """Targets (dx, dy, dw, dh[, dx', dw']) of reference boxes [R,4|6] w.r.t. proposals [R,4] (box_coder.py:21-50,83-116) or, for
+        6-coordinate reference boxes, w.r.t. proposals [R,6] whose right view codes dx', dw' (encode_x1y1x2y2x1px2p_fromboxes6, :51-85)."""
         wx, wy, ww, wh = self.weights
         ew, eh = proposals[:, 2] - proposals[:, 0] + 1, proposals[:, 3] - proposals[:, 1] + 1
         ex, ey = proposals[:, 0] + 0.5 * ew, proposals[:, 1] + 0.5 * eh
@@ -50,11 +51,15 @@ class BoxCoder:
         gx, gy = reference_boxes[:, 0] + 0.5 * gw, reference_boxes[:, 1] + 0.5 * gh
         cols = [wx * (gx - ex) / ew, wy * (gy - ey) / eh, ww * torch.log(gw / ew), wh * torch.log(gh / eh)]
         if reference_boxes.shape[1] == 6:
-            if proposals.shape[1] != 4:
-                raise ValueError("encode: 6-coordinate proposals are not used on this path")
+            ewp, exp = ew, ex
+            if proposals.shape[1] == 6:
+                ewp = proposals[:, 5] - proposals[:, 4] + 1
+                exp = proposals[:, 4] + 0.5 * ewp
+            elif proposals.shape[1] != 4:
+                raise ValueError('size(1) is not 4 or 6.')
             gwp = reference_boxes[:, 5] - reference_boxes[:, 4] + 1
             gxp = reference_boxes[:, 4] + 0.5 * gwp
-            cols += [wx * (gxp - ex) / ew, ww * torch.log(gwp / ew)]
+            cols += [wx * (gxp - exp) / ewp, ww * torch.log(gwp / ewp)]
         elif reference_boxes.shape[1] != 4:
             raise ValueError("size(1) is not 4 or 6.")
         return torch.stack(cols, dim=1)

@@ -81,6 +81,14 @@ _SIGS = {
     "drc_solver_prepare": (_I, [_L, _P, _I, _F, _I, _I, _P, _P, _P, _P, _P]),
     "drc_solver_sgd_step": (_I, [_L, _L, _I, _P, _P, _P, _P, _P, _I, _P]),
     "drc_solver_adam_step": (_I, [_L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "drc_det2d_max_gt": (_I, []),
+    "drc_det2d_max_images": (_I, []),
+    "drc_det2d_match_fwd": (_I, [_I, _P, _P, _I, _P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "drc_det2d_sample_fwd": (_I, [_I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "drc_det2d_srpn_loss_partials": (_L, [_I, _I, _I, _P]),
+    "drc_det2d_srpn_loss_fwd": (_I, [_I, _I, _I, _P, _L, _P, _P, _P, _P, _D, _P, _P, _P]),
+    "drc_det2d_fastrcnn_loss_fwd": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "drc_det2d_mask_loss_fwd": (_I, [_I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

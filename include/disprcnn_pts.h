@@ -405,6 +405,73 @@ int drc_solver_adam_step(int64_t n_chunks, int64_t n_tensors, int n_groups, cons
                          const float* hyper, const float* derived, const float* scalars, float* exp_avg, float* exp_avg_sq, int clip,
                          void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Training targets, balanced sampling and losses of the stereo 2D stage (det_train.hip; reference modeling/rpn/stereo_rpn/loss.py,
+ * roi_heads/box_head/loss.py, matcher.py, balanced_positive_negative_sampler.py, box_coder.py encode_*, utils/stereo_utils.py
+ * expand_left_right_box).  All images go in one launch: `cand_off` / `gt_off` are HOST arrays of N + 1 int32 CSR offsets (first 0,
+ * ascending) of the images' candidates and ground truths; N <= DRC_DET2D_MAX_IMAGES.  Decisions are fp32 in the reference's order, loss
+ * sums fp64 (per-block partials added in block order: bit-identical run to run).  No entry synchronises or reads back.
+ *
+ * drc_det2d_match_fwd -- boxlist_iou + Matcher(high, low, allow_low_quality) + labels + BoxCoder.encode for every candidate.
+ *   cand [R,cs]: cs = 4 anchors (xyxy) or cs = 6 joint proposals (x1 y1 x2 y2 x1' x2'; matched by the union of their two views and
+ *   encoded ..._fromboxes6); gt_left / gt_right [G,4]: the two views of the ground truths, matched by their union box and encoded from
+ *   original_lr_bbox = (left x1, union y1, left x2, union y2, right x1, right x2).  1 .. DRC_DET2D_MAX_GT ground truths and at least one
+ *   candidate per image, else -2.  Ties of the per-candidate maximum go to the lowest row.  allow_low_quality: gt_max [G] uint32 of
+ *   workspace receives each ground truth's largest IoU (an integer maximum of the bit patterns: order-free), and every candidate whose
+ *   IoU with a ground truth equals it keeps its best row (set_low_quality_matches_, ties and a maximum of 0 included).
+ *   matched [R] int64 = row within the image, -1 below `low`, -2 below `high`.  Label: gt_labels [G] int64 at the row clamped at 0, or 1
+ *   without gt_labels; 0 where matched is -1; -1 where it is -2 or where visibility [R] u8 (optional) is 0.  It is written as fp32
+ *   and / or int64, whichever pointers are given.  reg_targets [R,6] = (dx, dy, dw, dh, dx', dw') with weights4 = (wx, wy, ww, wh).
+ * drc_det2d_sample_fwd -- BalancedPositiveNegativeSampler with the randomness as an input: per image num_pos = min(#positives,
+ *   cap_pos), num_neg = min(#negatives, batch - num_pos); the members with the smallest (draws[i], i) keys are taken (radix select on
+ *   the bit pattern of the draw, draws >= 0; one workgroup per image and class).  labels: label_kind 0 fp32, 1 int64 (>= 1 positive, 0
+ *   negative, else ignored).  pos_mask / neg_mask [R] u8, counts [N,2] int32 = (num_pos, num_neg); sampled_idx (optional) [N,batch]
+ *   int64 = the image-local indices of pos | neg in ascending order, -1 past the count.
+ * drc_det2d_srpn_loss_fwd -- SRPNLossComputation's two losses and their gradients with respect to the RAW head maps.  levels: HOST
+ *   int64 [n_levels,7] = cls_logits [N,2A,H,W], bbox_pred [N,6A,H,W], grad of each (same shapes, every element written), H, W, offset of
+ *   the level's first anchor within an image (levels in order, anchors position-major: (y*W + x)*A + a); `total` anchors per image;
+ *   masks [N*total] as the sampler wrote them, reg_targets [N*total,6], counts [N,2].  The head's softmax pairs raw channel c with
+ *   c + A (srpn.py:47); the loss reads the probability map as (A,2): anchor a's vector is (p[2a], p[2a+1]) and the objective is
+ *   cross_entropy of THAT vector (a log-softmax of probabilities).  terms [3] = loss_objectness (mean over the sampled anchors),
+ *   loss_rpn_box_reg (smooth L1 with `beta` over the sampled positives' six codes, summed, over the sampled count), the count;
+ *   with no sampled anchor both losses and every gradient are 0.  partials: drc_det2d_srpn_loss_partials(...) doubles.
+ * drc_det2d_fastrcnn_loss_fwd -- cross_entropy(class_logits [R,C], labels [R] int64) and smooth L1 (beta 1) over columns 6*label ..
+ *   6*label+5 of box_regression [R,6C] against reg_targets [R,6] on rows with label > 0, both over R.  terms [3] = the two losses, R;
+ *   grad_logits / grad_box: every element written.  partials: 2 * ceil(R / 256) doubles.
+ * drc_det2d_mask_loss_fwd -- project_masks_on_boxes + binary_cross_entropy_with_logits of the mask head, one workgroup per ROI.  roi_off /
+ *   inst_off: HOST CSR offsets of the images' ROIs and instances.  boxes [P,4] xyxy; matched [P] int64 as drc_det2d_match_fwd wrote it
+ *   (no low-quality matches); inst_labels [I] int64; mask_logits [P,C,M,M]; masks: the instances' uint8 0/1 maps in one flat buffer,
+ *   table [I,3] int64 (device) = offset, H, W of each.  A ROI is positive when its match is not -1 and the instance at the matched row
+ *   clamped at 0 has a label in (0, C); the others drop out on the device (zero target, zero gradient).  Crop as BinaryMaskList.crop
+ *   (round half to even of the fp32 coordinate in double, the four clamps, at least one pixel), bilinear resize to M x M in the
+ *   arithmetic of torch's CPU upsample_bilinear2d (align_corners = False; mask_resize.h), truncated to uint8: 1 only where the value
+ *   reaches 1.0.  targets [P,M,M] u8; count [1] int32 = positive ROIs; terms [2] = the mean over their pixels of max(x,0) - x*t +
+ *   log1p(exp(-|x|)) (0 without a positive ROI), the pixel count; grad_logits [P,C,M,M] = (sigmoid(x) - t) / pixels on the ROI's class
+ *   plane, 0 elsewhere, every element written.  partials: P doubles.
+ * ------------------------------------------------------------------------------------- */
+#define DRC_DET2D_MAX_IMAGES 64
+#define DRC_DET2D_MAX_GT 128
+#define DRC_DET2D_MAX_LEVELS 8
+int drc_det2d_max_gt(void);
+int drc_det2d_max_images(void);
+int drc_det2d_match_fwd(int N, const int32_t* cand_off, const int32_t* gt_off, int cs, const float* cand, const float* gt_left,
+                        const float* gt_right, const int64_t* gt_labels, const uint8_t* visibility, float high, float low,
+                        int allow_low_quality, const float* weights4, uint32_t* gt_max, int64_t* matched, float* labels_f32,
+                        int64_t* labels_i64, float* reg_targets, void* stream);
+int drc_det2d_sample_fwd(int N, const int32_t* cand_off, const void* labels, int label_kind, const float* draws, int batch, int cap_pos,
+                         uint8_t* pos_mask, uint8_t* neg_mask, int32_t* counts, int64_t* sampled_idx, void* stream);
+int64_t drc_det2d_srpn_loss_partials(int N, int A, int n_levels, const int64_t* levels);
+int drc_det2d_srpn_loss_fwd(int N, int A, int n_levels, const int64_t* levels, int64_t total, const uint8_t* pos_mask,
+                            const uint8_t* neg_mask, const float* reg_targets, const int32_t* counts, double beta, double* partials,
+                            float* terms, void* stream);
+int drc_det2d_fastrcnn_loss_fwd(int R, int C, const float* class_logits, const int64_t* labels, const float* box_regression,
+                                const float* reg_targets, float* grad_logits, float* grad_box, double* partials, float* terms,
+                                void* stream);
+int drc_det2d_mask_loss_fwd(int N, const int32_t* roi_off, const int32_t* inst_off, int C, int M, const float* boxes,
+                            const int64_t* matched, const int64_t* inst_labels, const float* mask_logits, const uint8_t* masks,
+                            const int64_t* table, int32_t* count, uint8_t* targets, float* grad_logits, double* partials, float* terms,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
