@@ -61,8 +61,12 @@ def cell_anchors(stride, sizes, ratios):
 
 # ------------------------------------------------------------------------------------------------ box coder
 def decode(codes, boxes, weights):
-    """codes [R, K*4] or [R, K*6] (when boxes are [R,4] and 6 | width), boxes [R,4] xyxy -> same shape as codes."""
-    codes, boxes = codes.float(), boxes.float()
+    """codes [R, K*4] or [R, K*6] (when boxes are [R,4] and 6 | width), boxes [R,4] xyxy -> same shape as codes.
+    float32 like the reference, or float64 throughout when the codes are float64 (the edge tests' high-precision reference)."""
+    if codes.dtype == torch.float64:
+        boxes = boxes.double()
+    else:
+        codes, boxes = codes.float(), boxes.float()
     wx, wy, ww, wh = weights
     widths = boxes[:, 2] - boxes[:, 0] + 1
     heights = boxes[:, 3] - boxes[:, 1] + 1
