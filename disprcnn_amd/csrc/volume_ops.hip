@@ -745,24 +745,33 @@ int drc_conv3d_cout1_fwd(const float* x, const float* w, const float* res, float
     return done();
 }
 
+// Which kernel drc_upsample_softargmin_fwd runs for a shape (host only, launches nothing): 0 the generic kernel, 6 / 12 / 24 the
+// register-column template <D', 4 D'>; -2 / -3 where the launch entry returns them.  The launch entry dispatches on this value.
+int drc_upsample_softargmin_form(int Dp, int Hp, int Wp, int D, int H, int W) {
+    if (Dp <= 0 || Hp <= 0 || Wp <= 0 || D <= 0 || H <= 0 || W <= 0) return -2;
+    if (Dp > 96) return -3;  // LDS column per thread: Dp * 128 * 4 B
+    // the network's shapes (D = 4 D'): the register-column kernel, when 256 consecutive pixels touch at most 3 coarse rows and those fit LDS
+    if (D == 4 * Dp && H > 1 && W >= 86 && Wp <= 64 && (size_t)3 * Dp * Wp * 4 <= 64 * 1024) {
+        // 256 pixels span at most ceil(255 / W) + 1 <= 4 fine rows = a coarse extent of < 3 * sy + 1 < 2 rows + the bilinear neighbour
+        const float sy = (float)(Hp - 1) / (float)(H - 1);
+        if (sy * (float)((255 + W - 1) / W) < 1.f && (Dp == 6 || Dp == 12 || Dp == 24)) return Dp;
+    }
+    return 0;
+}
+
 int drc_upsample_softargmin_fwd(const float* cost, float* disp, int N, int Dp, int Hp, int Wp, int D, int H, int W, int mindisp,
                                 void* stream) {
-    if (N < 0 || Dp <= 0 || Hp <= 0 || Wp <= 0 || D <= 0 || H <= 0 || W <= 0) return -2;
-    if (Dp > 96) return -3;  // LDS column per thread: Dp * 128 * 4 B
+    if (N < 0) return -2;
+    int form = drc_upsample_softargmin_form(Dp, Hp, Wp, D, H, W);
+    if (form < 0) return form;
     const long total = (long)N * H * W;
     if (total == 0) return 0;
     if (!cost || !disp) return -1;
-    // the network's shapes (D = 4 D'): the register-column kernel, when 256 consecutive pixels touch at most 3 coarse rows and those fit LDS
-    if (D == 4 * Dp && H > 1 && W >= 86 && Wp <= 64 && (long)N * ((H * W + 255) / 256) < (1L << 31) && (size_t)3 * Dp * Wp * 4 <= 64 * 1024) {
-        // 256 pixels span at most ceil(255 / W) + 1 <= 4 fine rows = a coarse extent of < 3 * sy + 1 < 2 rows + the bilinear neighbour
-        const float sy = (float)(Hp - 1) / (float)(H - 1);
-        if (sy * (float)((255 + W - 1) / W) < 1.f) {
-            hipStream_t s = (hipStream_t)stream;
-            if (Dp == 12) return launch_softargmin_t<12, 48>(cost, disp, N, Hp, Wp, H, W, mindisp, s);
-            if (Dp == 24) return launch_softargmin_t<24, 96>(cost, disp, N, Hp, Wp, H, W, mindisp, s);
-            if (Dp == 6) return launch_softargmin_t<6, 24>(cost, disp, N, Hp, Wp, H, W, mindisp, s);
-        }
-    }
+    if ((long)N * ((H * W + 255) / 256) >= (1L << 31)) form = 0;      // the template's grid (a block per 256 pixels of a ROI) must fit
+    hipStream_t s = (hipStream_t)stream;
+    if (form == 12) return launch_softargmin_t<12, 48>(cost, disp, N, Hp, Wp, H, W, mindisp, s);
+    if (form == 24) return launch_softargmin_t<24, 96>(cost, disp, N, Hp, Wp, H, W, mindisp, s);
+    if (form == 6) return launch_softargmin_t<6, 24>(cost, disp, N, Hp, Wp, H, W, mindisp, s);
     const unsigned blocks = (unsigned)((total + kSAThreads - 1) / kSAThreads);
     hipLaunchKernelGGL(upsample_softargmin_kernel, dim3(blocks), dim3(kSAThreads), (size_t)Dp * kSAThreads * 4, (hipStream_t)stream, cost, disp, N, Dp, Hp, Wp, D, H, W, mindisp);
     return done();

@@ -236,6 +236,9 @@ int drc_conv3d_cout1_fwd(const float* x, const float* w, const float* res, float
  *   cost : dense [N,Dp,Hp,Wp]   disp : [N,H,W]   D = maxdisp-mindisp, d = mindisp..maxdisp-1 */
 int drc_upsample_softargmin_fwd(const float* cost, float* disp, int N, int Dp, int Hp, int Wp,
                                 int D, int H, int W, int mindisp, void* stream);
+/* The kernel the entry above runs for a shape (host only, nothing is launched): 0 = the generic kernel, 6 / 12 / 24 = the
+ * register-column template <D', 4 D'>; the entry's negative status (-2 bad shape, -3 D' > 96) where it returns one. */
+int drc_upsample_softargmin_form(int Dp, int Hp, int Wp, int D, int H, int W);
 
 /* Weight packing in one launch.  w: dense [Cout][Cin][K] (transposed = 0) or ConvTranspose [Cin][Cout][K] (transposed = 1); flip
  * reverses the tap order (data gradients).  out_tap: [K][cb_in][2][cout_pad][8] (drc_tapconv_fwd and the LDS-staged kernels);

@@ -593,3 +593,49 @@ def test_kernel_table_and_read_only_flags():
     with pytest.raises(AttributeError):
         pl.kernel.entry = "drc_tapconv_fwd"
 
+
+
+def test_softargmin_form_walks_the_dispatch_edges():
+    """drc_upsample_softargmin_form (host only): 0 = generic kernel, 6 / 12 / 24 = the register-column template, the launch entry's negative
+    status where it returns one.  Each pair sits either side of one term of the predicate; arguments are (Dp, Hp, Wp, D, H, W)."""
+    from disprcnn_amd import _lib
+    form = _lib.lib().drc_upsample_softargmin_form
+    assert form(12, 28, 28, 48, 112, 112) == 12 and form(24, 56, 56, 96, 224, 224) == 24 and form(6, 22, 22, 24, 88, 88) == 6
+    assert form(12, 7, 22, 48, 27, 85) == 0 and form(12, 7, 22, 48, 27, 86) == 12                    # W >= 86
+    assert form(24, 5, 64, 96, 19, 255) == 24 and form(24, 5, 65, 96, 19, 255) == 0                  # Wp <= 64
+    assert form(24, 5, 65, 96, 19, 257) == 0
+    assert form(12, 1, 30, 48, 1, 120) == 0 and form(12, 1, 30, 48, 2, 120) == 12                    # H > 1
+    assert form(12, 7, 22, 47, 27, 86) == 0 and form(12, 7, 22, 49, 27, 86) == 0                     # D == 4 Dp
+    assert form(12, 7, 22, 12, 27, 86) == 0 and form(12, 7, 22, 1, 27, 86) == 0
+    assert form(8, 7, 22, 32, 27, 86) == 0 and form(48, 7, 22, 192, 27, 86) == 0                     # D' without an instantiation
+    assert form(96, 2, 2, 384, 5, 5) == 0 and form(97, 2, 2, 388, 5, 5) == -3                        # Dp <= 96
+    assert form(96, 7, 22, 384, 27, 86) == 0 and form(97, 7, 22, 388, 27, 86) == -3
+    # sy * ceil(255 / W) < 1 with sy = (Hp-1)/(H-1) in fp32: W = 120 -> 3 fine rows, W = 86 -> 3, W = 255 -> 1, W = 128 -> 2
+    assert form(12, 5, 30, 48, 14, 120) == 12 and form(12, 6, 30, 48, 14, 120) == 0                  # 12/13 < 1 <= 15/13
+    assert form(12, 12, 30, 48, 14, 120) == 0
+    assert form(12, 2, 30, 48, 5, 120) == 12 and form(12, 2, 30, 48, 4, 120) == 0                    # 3/4 < 1 == fl(fl(1/3) * 3)
+    assert form(12, 10, 64, 48, 19, 255) == 12 and form(12, 19, 64, 48, 19, 255) == 0                # one fine row: sy < 1
+    assert form(12, 5, 32, 48, 10, 128) == 12 and form(12, 6, 32, 48, 10, 128) == 0                  # two fine rows: 8/9 < 1 <= 10/9
+    for bad in ((0, 7, 22, 48, 27, 86), (12, 0, 22, 48, 27, 86), (12, 7, 0, 48, 27, 86), (12, 7, 22, 0, 27, 86), (12, 7, 22, 48, 0, 86),
+                (12, 7, 22, 48, 27, 0), (-1, 7, 22, 48, 27, 86), (97, 0, 22, 388, 27, 86)):
+        assert form(*bad) == -2, bad
+    # the launch entry returns the same statuses before it looks at a pointer, and 0 for an empty batch
+    fwd = _lib.lib().drc_upsample_softargmin_fwd
+    assert fwd(None, None, 1, 97, 2, 2, 388, 5, 5, 0, None) == -3 and fwd(None, None, 1, 12, 0, 22, 48, 27, 86, 0, None) == -2
+    assert fwd(None, None, -1, 12, 7, 22, 48, 27, 86, 0, None) == -2 and fwd(None, None, 0, 12, 7, 22, 48, 27, 86, 0, None) == 0
+    assert fwd(None, None, 1, 12, 7, 22, 48, 27, 86, 0, None) == -1
+
+
+def test_softargmin_gpu_cases_cover_every_form():
+    """The case table of tests/test_hip_disp_tail.py names the kernel each case is meant for; the host query agrees, and each form has at
+    least two cases, one of them at amplitude 2000."""
+    from disprcnn_amd import _lib
+    from tests.test_hip_disp_tail import SA_CASES
+    form = _lib.lib().drc_upsample_softargmin_form
+    seen = {}
+    for c in SA_CASES:
+        assert form(c.Dp, c.Hp, c.Wp, c.D, c.H, c.W) == c.form, c
+        seen.setdefault(c.form, []).append(max(c.amps))
+    assert sorted(seen) == [0, 6, 12, 24]
+    for f, amps in seen.items():
+        assert len(amps) >= 2 and max(amps) == 2000.0, (f, amps)
