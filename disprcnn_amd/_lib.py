@@ -97,6 +97,13 @@ _SIGS = {
     "drc_linear_packed_floats": (C.c_int64, [_I, _I]),
     "drc_linear_pack_rows": (_I, [_P, _I, _I, _P, _P]),
     "drc_linear_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, C.c_int64, _P]),
+    "drc_linear_pack_cols": (_I, [_P, _I, _I, _P, _P]),
+    "drc_relu_dropout_fwd": (_I, [_P, _P, _P, C.c_int64, C.c_float, _I, _P]),
+    "drc_act_bwd_rows_scratch_doubles": (C.c_int64, [_I, _I]),
+    "drc_act_bwd_rows": (_I, [_P, _P, _P, C.c_float, _I, _I, _I, _I, _P, _P, _P, C.c_int64, _P]),
+    "drc_act_bwd_blocked_scratch_doubles": (C.c_int64, [_I, _I, _I]),
+    "drc_act_bwd_blocked": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, C.c_int64, _P]),
+    "drc_roi_align_fpn_bwd": (_I, [C.POINTER(DrcFpnPyramid), _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "drc_conv3d_k3_wino_rb_fwd": (_I, [C.POINTER(DrcTapconvParams), _P]),
     "drc_conv3d_k3_wino_rb_supported": (_I, [_I, _I, _I, _I]),
     "drc_conv2d_k3_wino_rb_supported": (_I, [_I, _I, _I]),

@@ -164,6 +164,31 @@ __global__ __launch_bounds__(256) void linear_pack_kernel(const float* __restric
     }
 }
 
+// The packed operand of a^T straight from row-major a[R][K] (no transposed copy in HBM): rows of the operand are a's columns, its reduction
+// axis is R.  out[(cb * RC + rc) * 256 + (g * 16 + c) * 4 + e] = a[rc * 16 + g * 4 + e][cb * 16 + c] (0 outside R x K); thread = one float4
+// of the output.  The 16 lanes c of a (g, e) read 64 contiguous bytes of one row of a; a 16 x 16 block of `a` is read exactly once.
+__global__ __launch_bounds__(256) void linear_pack_cols_kernel(const float* __restrict__ a, int R, int K, float* __restrict__ out) {
+    const int RC = (R + 15) >> 4;
+    const long total = (long)((K + 15) >> 4) * RC * 64;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int lane = (int)(i & 63);
+        const long blk = i >> 6;
+        const int rc = (int)(blk % RC);
+        const long cb = blk / RC;
+        const long col = cb * 16 + (lane & 15);
+        const long row = (long)rc * 16 + (lane >> 4) * 4;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (col < K) {
+            const float* src = a + row * K + col;
+            if (row < R) v.x = src[0];
+            if (row + 1 < R) v.y = src[K];
+            if (row + 2 < R) v.z = src[2L * K];
+            if (row + 3 < R) v.w = src[3L * K];
+        }
+        *(f32x4*)(out + i * 4) = v;
+    }
+}
+
 int pick_ksplit(int M, int N, int K) {
     const long tiles = (long)((M + 63) / 64) * ((N + 63) / 64);
     const int kchunks = (K + 15) / 16;
@@ -197,6 +222,17 @@ extern "C" int drc_linear_pack_rows(const float* a, int R, int K, float* out, vo
     long blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(linear_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, R, K, out);
+    return (int)hipGetLastError();
+}
+
+extern "C" int drc_linear_pack_cols(const float* a, int R, int K, float* out, void* stream) {
+    if (R < 0 || K <= 0) return -2;
+    if (R == 0) return 0;                                   // a^T has no columns: drc_linear_packed_floats(K, 0) = 0 floats
+    if (!a || !out) return -1;
+    const long total = drc_linear_packed_floats(K, R) / 4;
+    long blocks = (total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(linear_pack_cols_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, R, K, out);
     return (int)hipGetLastError();
 }
 

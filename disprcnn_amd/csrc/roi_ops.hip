@@ -101,9 +101,14 @@ __global__ __launch_bounds__(kThreads) void roi_align_fwd_kernel(const float* __
     }
 }
 
+// FPN = true: the adjoint of the one-launch pyramid forward -- roi k scatters into the gradient map of level levels[k] (`pyr.feat` then
+// holds the GRADIENT maps, zero-filled by the caller, and is written).  Same per-sample arithmetic; atomicAdd, so the order of the
+// additions -- and with it the last bits of the feature-map gradient -- is the schedule's.
+template <bool FPN>
 __global__ __launch_bounds__(kThreads) void roi_align_bwd_kernel(const float* __restrict__ gout, const float* __restrict__ rois,
-                                                                 float* __restrict__ gin, int K, int C, int H, int W, int PH, int PW,
-                                                                 float spatial_scale, int sampling_ratio) {
+                                                                 float* __restrict__ gin0, int K, int C, int H0, int W0, int PH, int PW,
+                                                                 float spatial_scale0, int sampling_ratio, const drc_fpn_pyramid pyr,
+                                                                 const int32_t* __restrict__ levels) {
     const long total = (long)K * C * PH * PW;
     for (long idx = (long)blockIdx.x * kThreads + threadIdx.x; idx < total; idx += (long)gridDim.x * kThreads) {
         long t = idx;
@@ -111,6 +116,10 @@ __global__ __launch_bounds__(kThreads) void roi_align_bwd_kernel(const float* __
         const int ph = (int)(t % PH); t /= PH;
         const int c = (int)(t % C);
         const int k = (int)(t / C);
+        const int lv = FPN ? levels[k] : 0;
+        float* gin = FPN ? const_cast<float*>(pyr.feat[lv]) : gin0;
+        const int H = FPN ? pyr.H[lv] : H0, W = FPN ? pyr.W[lv] : W0;
+        const float spatial_scale = FPN ? pyr.scale[lv] : spatial_scale0;
         const float* r = rois + (long)k * 5;
         const int b = (int)r[0];
         const float rsw = r[1] * spatial_scale, rsh = r[2] * spatial_scale;
@@ -314,8 +323,23 @@ int drc_roi_align_bwd(const float* grad_out, const float* rois, float* grad_in, 
     if (K == 0) return 0;
     if (!grad_out || !rois || !grad_in) return -1;   // grad_in must be zero-filled by the caller
     const long total = (long)K * C * PH * PW;
-    hipLaunchKernelGGL(roi_align_bwd_kernel, dim3(grid_for(total)), dim3(kThreads), 0, (hipStream_t)stream, grad_out, rois, grad_in, K, C,
-                       H, W, PH, PW, spatial_scale, sampling_ratio);
+    const drc_fpn_pyramid none = {};
+    hipLaunchKernelGGL(roi_align_bwd_kernel<false>, dim3(grid_for(total)), dim3(kThreads), 0, (hipStream_t)stream, grad_out, rois, grad_in, K, C,
+                       H, W, PH, PW, spatial_scale, sampling_ratio, none, nullptr);
+    return (int)hipGetLastError();
+}
+
+int drc_roi_align_fpn_bwd(const drc_fpn_pyramid* grad_pyr, const float* grad_out, const float* rois, const int32_t* levels, int K, int C, int PH,
+                          int PW, int sampling_ratio, void* stream) {
+    if (!grad_pyr) return -1;
+    if (K < 0 || C <= 0 || PH <= 0 || PW <= 0 || sampling_ratio < 0 || grad_pyr->n_levels < 1 || grad_pyr->n_levels > DRC_FPN_MAX_LEVELS) return -2;
+    for (int i = 0; i < grad_pyr->n_levels; ++i)
+        if (!grad_pyr->feat[i] || grad_pyr->H[i] <= 0 || grad_pyr->W[i] <= 0) return -2;
+    if (K == 0) return 0;
+    if (!grad_out || !rois || !levels) return -1;   // the gradient maps must be zero-filled by the caller
+    const long total = (long)K * C * PH * PW;
+    hipLaunchKernelGGL(roi_align_bwd_kernel<true>, dim3(grid_for(total)), dim3(kThreads), 0, (hipStream_t)stream, grad_out, rois, nullptr, K, C, 0,
+                       0, PH, PW, 0.f, sampling_ratio, *grad_pyr, levels);
     return (int)hipGetLastError();
 }
 

@@ -6,8 +6,9 @@ of generalized_rcnn.py:15-64) in its shipped stereo configuration (configs/kitti
 
 state_dict layout as in the reference: ``backbone.*``, ``rpn.*``, ``roi_heads.box.*``, ``roi_heads.mask.*`` (tests/test_detector2d.py
 checks the key sets of the heads against the reference's).  DISPNET_ON (the FPN-feature disparity head of the early fork, dispmodule.py)
-and DET3D_ON are separate models downstream and raise; training the 2D stage is not built (the shipped 3D configs freeze it:
-FIX_BACKBONE / FIX_RPN / FIX_BOX_HEAD)."""
+and DET3D_ON are separate models downstream and raise; training the whole 2D stage is not built (the shipped 3D configs freeze it:
+FIX_BACKBONE / FIX_RPN / FIX_BOX_HEAD) -- its ROI heads train on their own (roi_heads.StereoCombinedROIHeads), the trunk's backward, the
+Stereo RPN's training forward and the train-time proposal selection are missing."""
 from types import SimpleNamespace
 
 import torch
@@ -30,7 +31,8 @@ def default_cfg_2d(conv_body="R-101-FPN", num_classes=2, post_nms_top_n_test=300
         RPN=SimpleNamespace(USE_FPN=True, ANCHOR_SIZES=(32, 64, 128, 256, 512), ANCHOR_STRIDE=(4, 8, 16, 32, 64), ASPECT_RATIOS=(0.5, 1.0, 2.0),
                             STRADDLE_THRESH=0, PRE_NMS_TOP_N_TEST=6000, POST_NMS_TOP_N_TEST=post_nms_top_n_test, NMS_THRESH=0.7, MIN_SIZE=0,
                             FPN_POST_NMS_TOP_N_TEST=2000),
-        ROI_HEADS=SimpleNamespace(USE_FPN=True, BBOX_REG_WEIGHTS=(10.0, 10.0, 5.0, 5.0), SCORE_THRESH=0.05, NMS=0.5, DETECTIONS_PER_IMG=100),
+        ROI_HEADS=SimpleNamespace(USE_FPN=True, BBOX_REG_WEIGHTS=(10.0, 10.0, 5.0, 5.0), SCORE_THRESH=0.05, NMS=0.5, DETECTIONS_PER_IMG=100,
+                                  FG_IOU_THRESHOLD=0.5, BG_IOU_THRESHOLD=0.5, BATCH_SIZE_PER_IMAGE=512, POSITIVE_FRACTION=0.25),
         ROI_BOX_HEAD=SimpleNamespace(POOLER_RESOLUTION=7, POOLER_SCALES=scales, POOLER_SAMPLING_RATIO=0,
                                      FEATURE_EXTRACTOR="StereoFPN2MLPFeatureExtractor", PREDICTOR="StereoFPNPredictor", NUM_CLASSES=num_classes,
                                      MLP_HEAD_DIM=2048),
@@ -52,7 +54,9 @@ class DispRCNN(nn.Module):
 
     def forward(self, lrimages, lrtargets=None):
         if self.training:
-            raise NotImplementedError("training the 2D stage is not built (the shipped disparity / 3D configs freeze it)")
+            raise NotImplementedError("training the whole 2D stage is not built: the ROI heads train (StereoCombinedROIHeads), the trunk's "
+                                      "backward, the Stereo RPN's training forward and the train-time proposal selection are missing "
+                                      "(the shipped disparity / 3D configs freeze the stage)")
         left_images, right_images = to_image_list(lrimages["left"]), to_image_list(lrimages["right"])
         # the split-f16 layers of the trunk and of the RPN head report to ONE range guard, read once at the end of the stage; an overflow
         # (|v| > 65504: the fp32 reference has no such limit) repeats the stage on the fp32 kernels (engine.guarded)

@@ -1,6 +1,8 @@
 """Engine-backed layers of the 2D stage's heads: nn.Conv2d / nn.Linear parameter holders whose arithmetic runs on the HIP engine
 (convolutions: the same MFMA kernels as the backbone, bias in the folded-BN epilogue slot) or, for the fully connected layers, on the
-hand-written fp32-MFMA GEMM of csrc/linear.hip (round 3; rounds 1-2: torch.addmm -> hipBLASLt).  Inference only; there is no CPU path."""
+hand-written fp32-MFMA GEMM of csrc/linear.hip (round 3; rounds 1-2: torch.addmm -> hipBLASLt).  There is no CPU path.  The training
+forms (gemm_bias_act_train / linear_train, ConvReluChainTrain) are autograd Functions whose backward runs on the same kernels plus
+csrc/head_train.hip; the eval forms above them are untouched by training."""
 from collections import OrderedDict
 
 import torch
@@ -154,9 +156,14 @@ class BlockedConv2d:
             return E.guarded(self._guard, lambda: self._call_once(xb, yb), what="BlockedConv2d (split-f16 3x3 layer)")
         return self._call_once(xb, yb)
 
-    def _call_once(self, xb, yb):
+    def fp32(self, xb, yb):
+        """The same layer on the fp32 kernels only: no split-f16 bridge and no range guard (training: the backward differentiates
+        exactly the arithmetic the forward ran)."""
+        return self._call_once(xb, yb, bridge=False)
+
+    def _call_once(self, xb, yb, bridge=True):
         wp, sc, sh = self._weights(xb.device)
-        br = self._bridge(xb, yb)
+        br = self._bridge(xb, yb) if bridge else None
         if br is not None:
             from .. import s16 as S
             pk = self._s16["packs"]
@@ -247,3 +254,257 @@ def linear(x, layer, relu=False):
     or an nn.Conv2d that acts on a full window (its weight flattened to [out, in], K contiguous).  The weights are packed into the GEMM's
     operand layout once per parameter version, the activations per call.  GPU only."""
     return gemm_bias_act(x, layer.weight, lambda w: w.reshape(w.shape[0], -1), layer.bias, relu)
+
+
+# ------------------------------------------------------------------------------------------------ training forms
+def _pack_cols(a):
+    """The packed operand of a^T from row-major a [R, K] (drc_linear_pack_cols): no transposed copy in HBM."""
+    from .. import _lib
+    lib = _lib.lib()
+    R, K = a.shape
+    out = torch.empty(lib.drc_linear_packed_floats(K, R), dtype=torch.float32, device=a.device)
+    st = lib.drc_linear_pack_cols(E._ptr(a), R, K, E._ptr(out), E._stream_ptr(a.device))
+    _lib.check(st, "drc_linear_pack_cols")
+    return out
+
+
+def _gemm_packed(xp, wp, bias, M, N, K, relu, dev):
+    """drc_linear_fwd on operands that are packed already: y [M, N]."""
+    from .. import _lib
+    lib = _lib.lib()
+    y = torch.empty(M, N, dtype=torch.float32, device=dev)
+    if M == 0 or N == 0:
+        return y
+    nscr = lib.drc_linear_scratch_floats(M, N, K)
+    scr = E.scratch(dev, "linear", nscr) if nscr else None
+    st = lib.drc_linear_fwd(E._ptr(xp), E._ptr(wp), E._ptr(bias), E._ptr(y), M, N, K, int(bool(relu)), E._ptr(scr), nscr, E._stream_ptr(dev))
+    _lib.check(st, "drc_linear_fwd")
+    return y
+
+
+def _cached_pack(weight_param, w2, tag, pack):
+    """pack(w2) cached per live parameter object and tag, rebuilt when the parameter's version, storage, device or shape changes."""
+    key = (weight_param._version, weight_param.data_ptr(), w2.device, tuple(weight_param.shape))
+    cache = _packed_cache(weight_param)
+    ent = cache.get(tag)
+    if ent is None or ent[0] != key:
+        ent = cache[tag] = (key, pack(w2.detach().to(torch.float32).contiguous()), tuple(w2.shape))
+    return ent[1]
+
+
+def relu_dropout(x, draws, p, relu=True):
+    """max(x, 0) . [draws >= (float)p] / (1 - p) in place on row-major x (drc_relu_dropout_fwd); p = 0 ignores draws."""
+    from .. import _lib
+    st = _lib.lib().drc_relu_dropout_fwd(E._ptr(x), E._ptr(draws) if p > 0 else None, E._ptr(x), x.numel(), float(p), int(bool(relu)),
+                                         E._stream_ptr(x.device))
+    _lib.check(st, "drc_relu_dropout_fwd")
+    return x
+
+
+def act_bwd_rows(dy, y, draws, p, relu, want_db=True, fold=1):
+    """dz = dy . [y > 0] . keep / (1 - p) and db = column sums of dz (fp64, fixed order; `fold` columns per entry) for row-major [M, N]."""
+    from .. import _lib
+    lib = _lib.lib()
+    M, N = dy.shape
+    dev = dy.device
+    dz = torch.empty_like(dy)
+    db = torch.empty(N // fold, dtype=torch.float32, device=dev) if want_db else None
+    nd = lib.drc_act_bwd_rows_scratch_doubles(M, N) if want_db else 0
+    scr = E.scratch(dev, "act_bwd", 2 * nd) if nd else None           # (float workspace: two floats per double)
+    st = lib.drc_act_bwd_rows(E._ptr(dy), E._ptr(y) if relu else None, E._ptr(draws) if p > 0 else None, float(p), int(bool(relu)), M, N, int(fold),
+                              E._ptr(dz), E._ptr(db), E._ptr(scr), nd, E._stream_ptr(dev))
+    _lib.check(st, "drc_act_bwd_rows")
+    return dz, db
+
+
+def act_bwd_blocked(dy, y, relu, dz, want_db=True):
+    """dz = dy . [y > 0] on Blocked tensors of one geometry (2D: D = 1) and the per-channel sums of dz over all units and pixels."""
+    from .. import _lib
+    lib = _lib.lib()
+    for t in (y, dz):
+        if (t.N, t.C, t.D, t.H, t.W, t.pd, t.ph, t.pw) != (dy.N, dy.C, dy.D, dy.H, dy.W, dy.pd, dy.ph, dy.pw):
+            raise ValueError("act_bwd_blocked: dy, y and dz must share one geometry")
+    if dy.D != 1 or dy.pd != 0:
+        raise NotImplementedError("act_bwd_blocked: 2D blocked tensors")
+    dev = dy.device
+    db = torch.empty(dy.cb * 16, dtype=torch.float32, device=dev) if want_db else None
+    nd = lib.drc_act_bwd_blocked_scratch_doubles(dy.N, dy.C, dy.H) if want_db else 0
+    scr = E.scratch(dev, "act_bwd", 2 * nd) if nd else None
+    st = lib.drc_act_bwd_blocked(E._ptr(dy.storage), E._ptr(y.storage), int(bool(relu)), dy.N, dy.C, dy.H, dy.W, dy.ph, dy.pw, E._ptr(dz.storage),
+                                 E._ptr(db), E._ptr(scr), nd, E._stream_ptr(dev))
+    _lib.check(st, "drc_act_bwd_blocked")
+    return dz, (db[: dy.C] if want_db else None)
+
+
+class _GemmBiasActTrain(torch.autograd.Function):
+    """y = dropout_p(act(x @ w2^T + bias)) with its backward on the same GEMM.  w2 [N, K] is a (differentiable) 2D view of the layer's
+    weight, `weight_param` the parameter it came from (the key of the packed-operand cache), bias [N / fold] is repeated `fold` times
+    along N (the 2x2 transposed convolution's taps).  Saved: x, the OUTPUT y (its sign is the ReLU mask) and the draws."""
+
+    @staticmethod
+    def forward(ctx, x, w2, bias, weight_param, tag, relu, p, draws, fold):
+        dev = x.device
+        N, K = w2.shape
+        M = x.shape[0]
+        wp = _cached_pack(weight_param, w2, tag, _pack_rows)
+        b = None
+        if bias is not None:
+            b = bias.detach().to(device=dev, dtype=torch.float32)
+            b = (b.repeat_interleave(fold) if fold > 1 else b).contiguous()
+        y = _gemm_packed(_pack_rows(x), wp, b, M, N, K, relu, dev) if M else torch.empty(0, N, dtype=torch.float32, device=dev)
+        if p > 0 and M:
+            relu_dropout(y, draws, p, relu)
+        ctx.save_for_backward(x, y, draws if p > 0 else None, w2)
+        ctx.cfg = (weight_param, tag, bool(relu), float(p), int(fold), bias is not None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, y, draws, w2 = ctx.saved_tensors
+        weight_param, tag, relu, p, fold, has_bias = ctx.cfg
+        dev = dy.device
+        M, K = x.shape
+        N = w2.shape[0]
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
+        if M == 0:
+            return (x.new_zeros(0, K) if need_x else None, torch.zeros_like(w2) if need_w else None,
+                    torch.zeros(N // fold, dtype=torch.float32, device=dev) if need_b else None, None, None, None, None, None, None)
+        dy = dy.float().contiguous()
+        if relu or p > 0 or need_b:
+            dz, db = act_bwd_rows(dy, y, draws, p, relu, want_db=need_b, fold=fold)
+        else:
+            dz, db = dy, None
+        dx = dw = None
+        if need_x:                                             # dX [M, K] = dZ [M, N] . W [N, K]
+            wtp = _cached_pack(weight_param, w2, tag + "^T", _pack_cols)
+            dx = _gemm_packed(_pack_rows(dz), wtp, None, M, K, N, False, dev)
+        if need_w:                                             # dW [N, K] = dZ^T . X, reduction over the M rows
+            dw = _gemm_packed(_pack_cols(dz), _pack_cols(x), None, N, K, M, False, dev)
+        return dx, dw, db, None, None, None, None, None, None
+
+
+def gemm_bias_act_train(x, weight_param, w2d_fn, bias, relu, tag="", p=0.0, draws=None, bias_fold=1):
+    """The training form of gemm_bias_act: dropout_p(act(x [M,K] @ W^T + bias)) as an autograd Function -- forward on drc_linear_fwd (+
+    drc_relu_dropout_fwd where p > 0: element (m, n) is kept iff draws[m][n] >= (float)p and scaled by 1 / (1 - p)), backward =
+    drc_act_bwd_rows (ReLU / dropout mask and the fp64 fixed-order bias gradient) + two more drc_linear_fwd calls on operands
+    drc_linear_pack_cols transposes while packing.  The data-gradient GEMM is skipped when x needs no gradient.  Every result has the same
+    bits run to run.  The packed W^T is cached per parameter version next to the packed W (tag + '^T'): for the box head's 25088 -> 2048
+    layer that is a SECOND 205 MB copy of the weight on the device."""
+    E.require_gpu(x, "gemm_bias_act_train")
+    x = x.float().contiguous()
+    w2 = w2d_fn(weight_param)
+    if w2.shape[1] != x.shape[1]:
+        raise ValueError(f"gemm_bias_act_train: input has {x.shape[1]} features, the layer expects {w2.shape[1]}")
+    p = float(p)
+    if p > 0:
+        if draws is None:
+            draws = torch.rand(x.shape[0], w2.shape[0], dtype=torch.float32, device=x.device)
+        draws = draws.to(device=x.device, dtype=torch.float32).contiguous()
+        if tuple(draws.shape) != (x.shape[0], w2.shape[0]):
+            raise ValueError(f"gemm_bias_act_train: draws {tuple(draws.shape)} for an output of {(x.shape[0], w2.shape[0])}")
+    else:
+        draws = None
+    return _GemmBiasActTrain.apply(x, w2, bias, weight_param, tag, relu, p, draws, int(bias_fold))
+
+
+def linear_train(x, layer, relu=False, p=0.0, draws=None):
+    """The training form of linear(): see gemm_bias_act_train."""
+    return gemm_bias_act_train(x, layer.weight, lambda w: w.reshape(w.shape[0], -1), layer.bias, relu, p=p, draws=draws)
+
+
+class ConvReluChainTrain:
+    """The training form of a chain of conv3x3 + bias + ReLU layers (the mask head's feature extractor) on the engine's blocked layout.
+    Forward: every layer's blocked activation is KEPT (no ping-pong), fp32 kernels only (BlockedConv2d.fp32).  Backward, per layer in
+    reverse: drc_act_bwd_blocked (ReLU mask + the per-channel bias gradient, fp64 in a fixed order), the weight gradient on
+    drc_tapconv_wgrad (psmnet.train.wgrad, fixed-order partials), the data gradient on the engine's stride-1 convolution plan with swapped
+    and flipped weights -- as psmnet.train does for stride-1 2D layers.  Every parameter gradient has the same bits run to run.
+
+    The activations live in storage this object owns, per map geometry and sized for a capacity bucket of the unit count; a later
+    forward of the same geometry overwrites them, so backward() of an EARLIER forward raises instead of differentiating stale values."""
+
+    def __init__(self, convs, engines):
+        self.convs, self.engines = list(convs), list(engines)
+        for c in self.convs:
+            if (c.kernel_size, c.stride, c.padding, c.dilation, c.groups) != ((3, 3), (1, 1), (1, 1), (1, 1), 1) or c.bias is None:
+                raise NotImplementedError("ConvReluChainTrain: conv3x3 / stride 1 / pad 1 layers with a bias")
+        self._bufs, self._gen, self._dw = {}, 0, {}
+
+    def _storage(self, n, h, w, dev):
+        key = (h, w, dev)
+        buf = self._bufs.get(key)
+        chans = [self.convs[0].in_channels] + [c.out_channels for c in self.convs]
+        if buf is None or buf["cap"] < n:
+            cap = E.bucket_units(n)
+            buf = self._bufs[key] = dict(cap=cap, acts=[E.Blocked(cap, ch, 1, h, w, 0, 1, 1, dev) for ch in chans],
+                                         grads=[E.Blocked(cap, max(chans), 1, h, w, 0, 1, 1, dev) for _ in range(2)])
+            while len(self._bufs) > 4:
+                self._bufs.pop(next(iter(self._bufs)))
+        if len(set(chans)) != 1:
+            raise NotImplementedError("ConvReluChainTrain: layers of one width (the shipped CONV_LAYERS are 256 throughout)")
+        view = lambda b, ch: E.Blocked(n, ch, 1, h, w, 0, 1, 1, dev, storage=b.storage)
+        return [view(b, ch) for b, ch in zip(buf["acts"], chans)], [view(b, chans[0]) for b in buf["grads"]]
+
+    def _dgrad_weights(self, conv, plan, dev):
+        """swapped (in <-> out) and tap-flipped packings of conv.weight for the data-gradient plan, per parameter version"""
+        key = (conv.weight._version, conv.weight.data_ptr(), dev, plan.pack_kind)
+        ent = self._dw.get(id(conv))
+        if ent is None or ent[0] != key:
+            wt = conv.weight.detach().to(device=dev, dtype=torch.float32)
+            if plan.pack_kind in ("tap", "t16"):
+                wp, w16 = E.pack_layouts(wt, True, True, want_t16=plan.needs_t16)
+            else:
+                wp, w16 = E.pack_layouts(wt, True, True, want_t16=False)[0], plan.pack16(wt, True, True)
+            cp = E.cout_pad_of(conv.in_channels)
+            ent = self._dw[id(conv)] = (key, wp, w16, torch.ones(cp, device=dev), torch.zeros(cp, device=dev))
+        return ent[1:]
+
+    def __call__(self, x):
+        """x dense [n, C, h, w] (n >= 1) -> dense [n, C_out, h, w], differentiable in x and in every layer's weight and bias."""
+        params = [p for c in self.convs for p in (c.weight, c.bias)]
+        return _ConvReluChainFn.apply(x, self, *params)
+
+
+class _ConvReluChainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, chain, *params):
+        E.require_gpu(x, "ConvReluChainTrain")
+        n, _, h, w = x.shape
+        acts, grads = chain._storage(n, h, w, x.device)
+        acts[0].from_dense(x.float())
+        for eng, src, dst in zip(chain.engines, acts[:-1], acts[1:]):
+            eng.fp32(src, dst)
+        chain._gen += 1
+        ctx.chain, ctx.acts, ctx.gbuf, ctx.gen = chain, acts, grads, chain._gen
+        return acts[-1].to_dense()[:, :, 0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        from .psmnet.train import wgrad
+        chain, acts, (ga, gb) = ctx.chain, ctx.acts, ctx.gbuf
+        if ctx.gen != chain._gen:
+            raise RuntimeError("ConvReluChainTrain: a later forward has overwritten the activations this backward needs")
+        dev = gout.device
+        L = len(chain.convs)
+        cls = dict(n=(1, 3, 3), first=(0, 0, 0), step=(1, 1, 1))            # taps of a 3x3 / pad 1 layer on a halo-1 input (engine.taps_conv)
+        out = [None] * (2 * L)
+        ga.from_dense(gout.float().contiguous())
+        for i in reversed(range(L)):
+            conv = chain.convs[i]
+            dz, db = act_bwd_blocked(ga, acts[i + 1], True, gb)
+            gw = wgrad(acts[i], dz, cls, 1)                                    # [ci][co][t]
+            out[2 * i] = gw[: conv.in_channels, : conv.out_channels].permute(1, 0, 2).reshape(conv.weight.shape)
+            out[2 * i + 1] = db
+            if i > 0 or ctx.needs_input_grad[0]:
+                plans = chain.__dict__.setdefault("_dplans", OrderedDict())
+                key = (i, dz.N, dz.H, dz.W, dev)
+                plan = plans.get(key)
+                if plan is None:
+                    plan = plans[key] = E.plan_conv2d(dz, ga, 3, 1, 1, 1, conv.in_channels, False)
+                    while len(plans) > 32:
+                        plans.popitem(last=False)
+                wp, w16, ones, zeros = chain._dgrad_weights(conv, plan, dev)
+                plan.run(dz, wp, ones, zeros, ga, None, w16=w16)
+        gx = ga.to_dense()[:, :, 0] if ctx.needs_input_grad[0] else None
+        return (gx, None) + tuple(out)

@@ -24,6 +24,47 @@ class LevelMapper:
         return torch.clamp(lv, min=self.k_min, max=self.k_max).to(torch.int64) - int(self.k_min)
 
 
+def _pyramid(maps, scales):
+    pyr = _lib.DrcFpnPyramid()
+    pyr.n_levels = len(maps)
+    for i, (f, s) in enumerate(zip(maps, scales)):
+        pyr.feat[i], pyr.H[i], pyr.W[i], pyr.scale[i] = f.data_ptr(), f.shape[2], f.shape[3], s
+    return pyr
+
+
+def _fpn_forward(feats, scales, rois, lv32, output_size, sampling_ratio):
+    c = feats[0].shape[1]
+    out = torch.empty(len(rois), c, *output_size, dtype=torch.float32, device=rois.device)
+    st = _lib.lib().drc_roi_align_fpn_fwd(C.byref(_pyramid(feats, scales)), E._ptr(rois), E._ptr(lv32), E._ptr(out), len(rois), c, output_size[0],
+                                          output_size[1], int(sampling_ratio), E._stream_ptr(rois.device))
+    _lib.check(st, "drc_roi_align_fpn_fwd")
+    return out
+
+
+class _FpnROIAlign(torch.autograd.Function):
+    """The one-launch pyramid ROIAlign with its one-launch adjoint (drc_roi_align_fpn_bwd): roi k scatters into the gradient map of its
+    level.  atomicAdd, as the single-level kernel and the reference: the feature-map gradient is NOT bit-reproducible run to run (every
+    parameter gradient of the heads is).  No host read in either direction."""
+
+    @staticmethod
+    def forward(ctx, rois, lv32, scales, output_size, sampling_ratio, *feats):
+        ctx.save_for_backward(rois, lv32)
+        ctx.cfg = (scales, output_size, sampling_ratio, [tuple(f.shape) for f in feats])
+        return _fpn_forward(feats, scales, rois, lv32, output_size, sampling_ratio)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        rois, lv32 = ctx.saved_tensors
+        scales, output_size, sampling_ratio, shapes = ctx.cfg
+        gout = gout.float().contiguous()
+        grads = [torch.zeros(s, dtype=torch.float32, device=gout.device) for s in shapes]
+        st = _lib.lib().drc_roi_align_fpn_bwd(C.byref(_pyramid(grads, scales)), E._ptr(gout), E._ptr(rois), E._ptr(lv32), len(rois), shapes[0][1],
+                                              output_size[0], output_size[1], int(sampling_ratio), E._stream_ptr(gout.device))
+        _lib.check(st, "drc_roi_align_fpn_bwd")
+        return (None, None, None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[5:]))
+
+
 class Pooler(nn.Module):
     def __init__(self, output_size, scales, sampling_ratio):
         super().__init__()
@@ -31,6 +72,7 @@ class Pooler(nn.Module):
         self.output_size = tuple(output_size)
         self.map_levels = LevelMapper(-math.log2(scales[0]), -math.log2(scales[-1]))
         self.single_launch = True        # all levels in one drc_roi_align_fpn_fwd launch (False: the reference's per-level loop)
+        self.last_path = None            # the path the last forward took: 'single_level' | 'fpn' | 'fpn_autograd' | 'per_level' (tests)
 
     @staticmethod
     def convert_to_roi_format(boxes):
@@ -43,26 +85,27 @@ class Pooler(nn.Module):
         rois = self.convert_to_roi_format(boxes)
         c = x[0].shape[1]
         if len(self.poolers) == 1:
+            self.last_path = "single_level"
             return self.poolers[0](x[0], rois)
         if len(rois) == 0:
+            self.last_path = None
             return torch.zeros(0, c, *self.output_size, dtype=torch.float32, device=x[0].device)
         levels = self.map_levels(boxes)
         feats = [f.contiguous() for f in x[: len(self.poolers)]]
         needs_grad = torch.is_grad_enabled() and any(f.requires_grad for f in feats)
-        if not needs_grad and self.single_launch and all(f.is_cuda and f.dtype == torch.float32 and f.shape[1] == c for f in feats) and len(feats) <= 8:
-            # one launch over the pyramid (drc_roi_align_fpn_fwd): every roi reads its level's map and scale; no per-level host sync
-            pyr = _lib.DrcFpnPyramid()
-            pyr.n_levels = len(feats)
-            for i, f in enumerate(feats):
-                pyr.feat[i], pyr.H[i], pyr.W[i] = f.data_ptr(), f.shape[2], f.shape[3]
-                pyr.scale[i] = f.shape[2] / boxes[0].height                     # (fork quirk: feature height / image height)
+        if self.single_launch and all(f.is_cuda and f.dtype == torch.float32 and f.shape[1] == c for f in feats) and len(feats) <= 8:
+            # one launch over the pyramid (drc_roi_align_fpn_fwd): every roi reads its level's map and scale; no per-level host sync.
+            # Features that require grad go through the autograd Function, whose backward is one launch as well.
+            scales = tuple(f.shape[2] / boxes[0].height for f in feats)         # (fork quirk: feature height / image height)
             lv32 = levels.to(torch.int32).contiguous()
             rois = rois.contiguous()
-            out = torch.empty(len(rois), c, *self.output_size, dtype=torch.float32, device=rois.device)
-            st = _lib.lib().drc_roi_align_fpn_fwd(C.byref(pyr), E._ptr(rois), E._ptr(lv32), E._ptr(out), len(rois), c, self.output_size[0],
-                                                  self.output_size[1], int(self.poolers[0].sampling_ratio), E._stream_ptr(rois.device))
-            _lib.check(st, "drc_roi_align_fpn_fwd")
-            return out
+            sr = int(self.poolers[0].sampling_ratio)
+            if needs_grad:
+                self.last_path = "fpn_autograd"
+                return _FpnROIAlign.apply(rois, lv32, scales, self.output_size, sr, *feats)
+            self.last_path = "fpn"
+            return _fpn_forward(feats, scales, rois, lv32, self.output_size, sr)
+        self.last_path = "per_level"
         out = torch.zeros(len(rois), c, *self.output_size, dtype=torch.float32, device=x[0].device)       # (the per-level path only)
         for level, (feat, pooler) in enumerate(zip(x[: len(self.poolers)], self.poolers)):
             idx = torch.nonzero(levels == level).reshape(-1)

@@ -1,4 +1,5 @@
-"""Stereo ROI box head -- drop-in for ``disprcnn.modeling.roi_heads.box_head`` in its shipped configuration (inference):
+"""Stereo ROI box head -- drop-in for ``disprcnn.modeling.roi_heads.box_head`` in its shipped configuration, inference and the training
+step (box_head.py:75-127: subsample, feature extractor with Dropout, predictor, loss evaluator; ROIBoxHead.forward / losses_on_sampled):
 ROIBoxHead.forward_double_view (box_head.py:67-121) = StereoFPN2MLPFeatureExtractor (roi_box_feature_extractors.py:85-120) +
 StereoFPNPredictor (roi_box_predictors.py:61-83) + PostProcessor.forward_double_view (inference.py:84-120, 213-263).
 
@@ -13,7 +14,7 @@ from torch import nn
 from ...structures.bounding_box import BoxList
 from ...structures.boxlist_ops import cat_boxlist, double_view_boxlist_nms
 from ..box_coder import BoxCoder
-from ..head_ops import linear
+from ..head_ops import linear, linear_train
 from ..poolers import Pooler
 
 
@@ -28,12 +29,21 @@ class StereoFPN2MLPFeatureExtractor(nn.Module):
                                       nn.Dropout(p=0.2))
         self.out_channels = rep
 
-    def forward(self, x, proposals):
-        if self.training:
-            raise NotImplementedError("box head training is not built")
+    def forward(self, x, proposals, dropout_draws=None):
+        """Training: fc + ReLU + Dropout twice as autograd Functions (head_ops.linear_train), p of RCNN_top[2] / RCNN_top[5];
+        dropout_draws is fp32 [2][R][MLP_HEAD_DIM] uniform draws (element kept iff draw >= p), None = one torch.rand call."""
         lx = self.pooler(x["left"], proposals["left"])
         rx = self.pooler(x["right"], proposals["right"])
         t = torch.cat([lx, rx], dim=1).flatten(1)                  # [R, 2C*7*7]: the 7x7/7 convolution sees the whole window
+        if self.training:
+            if not t.is_cuda:
+                raise RuntimeError("StereoFPN2MLPFeatureExtractor: expected CUDA/HIP tensors on an MI355X; the HIP path has no CPU fallback")
+            if dropout_draws is None:
+                dropout_draws = torch.rand(2, t.shape[0], self.out_channels, dtype=torch.float32, device=t.device)
+            if tuple(dropout_draws.shape) != (2, t.shape[0], self.out_channels):
+                raise ValueError(f"dropout draws {tuple(dropout_draws.shape)} for {t.shape[0]} ROIs of {self.out_channels} features")
+            t = linear_train(t, self.RCNN_top[0], relu=True, p=self.RCNN_top[2].p, draws=dropout_draws[0])
+            return linear_train(t, self.RCNN_top[3], relu=True, p=self.RCNN_top[5].p, draws=dropout_draws[1])
         t = linear(t, self.RCNN_top[0], relu=True)
         return linear(t, self.RCNN_top[3], relu=True)               # the mean over the 1x1 map is the identity
 
@@ -51,6 +61,8 @@ class StereoFPNPredictor(nn.Module):
 
     def forward(self, x):
         x = x.flatten(1)
+        if self.training:
+            return linear_train(x, self.cls_score), linear_train(x, self.bbox_pred)
         return linear(x, self.cls_score), linear(x, self.bbox_pred)
 
 
@@ -120,10 +132,48 @@ class ROIBoxHead(nn.Module):
         self.predictor = StereoFPNPredictor(cfg, self.feature_extractor.out_channels)
         self.post_processor = PostProcessor(h.SCORE_THRESH, h.NMS, h.DETECTIONS_PER_IMG, BoxCoder(weights=h.BBOX_REG_WEIGHTS),
                                             cfg.MODEL.CLS_AGNOSTIC_BBOX_REG)
+        self._cfg, self._loss_evaluator = cfg, None
 
-    def forward(self, features, proposals, targets=None):
+    @property
+    def loss_evaluator(self):
+        """make_roi_box_loss_evaluator(cfg), built on first use: the evaluator holds no parameters or buffers (no state-dict keys), and
+        a config without the sampler's keys (FG_IOU_THRESHOLD, BG_IOU_THRESHOLD, BATCH_SIZE_PER_IMAGE, POSITIVE_FRACTION) still
+        constructs and runs the head in eval; those keys then take the reference defaults 0.5 / 0.5 / 512 / 0.25."""
+        if self._loss_evaluator is None:
+            from types import SimpleNamespace
+            from .box_head_loss import make_roi_box_loss_evaluator
+            h = self._cfg.MODEL.ROI_HEADS
+            heads = SimpleNamespace(FG_IOU_THRESHOLD=getattr(h, "FG_IOU_THRESHOLD", 0.5), BG_IOU_THRESHOLD=getattr(h, "BG_IOU_THRESHOLD", 0.5),
+                                    BATCH_SIZE_PER_IMAGE=getattr(h, "BATCH_SIZE_PER_IMAGE", 512),
+                                    POSITIVE_FRACTION=getattr(h, "POSITIVE_FRACTION", 0.25), BBOX_REG_WEIGHTS=h.BBOX_REG_WEIGHTS)
+            self._loss_evaluator = make_roi_box_loss_evaluator(SimpleNamespace(MODEL=SimpleNamespace(
+                ROI_HEADS=heads, CLS_AGNOSTIC_BBOX_REG=self._cfg.MODEL.CLS_AGNOSTIC_BBOX_REG)))
+        return self._loss_evaluator
+
+    def losses_on_sampled(self, features, left_sampled, right_sampled, labels, regression_targets, dropout_draws=None):
+        """The training step after sampling: features {'left', 'right'} pyramids, the sampled per-image BoxLists of both views, labels [R]
+        int64 and regression_targets [R,6] of all images concatenated -> (x, class_logits, box_regression, {'loss_classifier',
+        'loss_box_reg'}).  backward() of the losses fills the six parameter gradients (bit-identical run to run) and, where the pyramids
+        require grad, theirs (atomicAdd: not bit-reproducible)."""
+        from ...layers import det2d_loss as D
+        x = self.feature_extractor(features, {"left": left_sampled, "right": right_sampled}, dropout_draws)
+        class_logits, box_regression = self.predictor(x)
+        loss_cls, loss_box, _ = D.fastrcnn_loss(class_logits, box_regression, labels, regression_targets)
+        return x, class_logits, box_regression, dict(loss_classifier=loss_cls, loss_box_reg=loss_box)
+
+    def forward(self, features, proposals, targets=None, draws=None):
+        """Training (reference box_head.py:75-127): subsample under no_grad, feature extractor, predictor, loss evaluator ->
+        (x, left_sampled, right_sampled, losses).  draws: optional dict, 'sample' = what subsample takes, 'dropout' = fp32
+        [2][R][MLP_HEAD_DIM]; a missing entry is one torch.rand call."""
         if self.training:
-            raise NotImplementedError("box head training (sampling, losses) belongs to the 2D stage's training, which is not built")
+            if not all(f.is_cuda for f in list(features["left"]) + list(features["right"])):
+                raise RuntimeError("ROIBoxHead: expected CUDA/HIP tensors on an MI355X; the HIP path has no CPU fallback")
+            draws = draws or {}
+            ev = self.loss_evaluator
+            with torch.no_grad():
+                left, right = ev.subsample(proposals, targets, draws.get("sample"))
+            x, _, _, losses = self.losses_on_sampled(features, left, right, ev._labels, ev._regression_targets, draws.get("dropout"))
+            return x, left, right, losses
         x = self.feature_extractor(features, proposals)
         class_logits, box_regression = self.predictor(x)
         left, right = self.post_processor((class_logits, box_regression), proposals)

@@ -293,6 +293,11 @@ int drc_roi_align_fpn_fwd(const drc_fpn_pyramid* pyr, const float* rois, const i
                           int sampling_ratio, void* stream);
 int drc_roi_align_bwd(const float* grad_out, const float* rois, float* grad_in, int K, int C, int H, int W, int PH, int PW,
                       float spatial_scale, int sampling_ratio, void* stream);
+/* The adjoint of drc_roi_align_fpn_fwd in one launch: roi k scatters into the gradient map of level levels[k].  `grad_pyr` has the
+ * forward's geometry and scales, its feat[] point at the per-level GRADIENT maps [N,C,H,W] (zero-filled by the caller; they are written).
+ * atomicAdd like drc_roi_align_bwd and the reference: the feature-map gradient is not bit-reproducible run to run. */
+int drc_roi_align_fpn_bwd(const drc_fpn_pyramid* grad_pyr, const float* grad_out, const float* rois, const int32_t* levels, int K, int C, int PH,
+                          int PW, int sampling_ratio, void* stream);
 
 /* Left/right ROI alignment of DispRCNN3D.prepare_psmnet_input_and_target (disprcnn3d.py:118-146) on the device:
  * expand_box_to_integer (stereo_utils.py:219-229), clamps, common width.
@@ -544,6 +549,25 @@ int drc_linear_pack_rows(const float* a, int R, int K, float* out, void* stream)
 int64_t drc_linear_scratch_floats(int M, int N, int K);
 int drc_linear_fwd(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int relu, float* scratch,
                    int64_t scratch_floats, void* stream);
+/* Training of the same layers.  drc_linear_pack_cols writes the packed operand of a^T (drc_linear_packed_floats(K, R) floats) straight from
+ * row-major a[R][K], so both backward GEMMs are drc_linear_fwd calls:
+ *   dX[R][in] = dZ . W     : x = pack_rows(dZ), w = pack_cols(W),  (M, N, K) = (R, in, out)
+ *   dW[out][in] = dZ^T . X : x = pack_cols(dZ), w = pack_cols(X),  (M, N, K) = (out, in, R)
+ * drc_relu_dropout_fwd: y = max(x, 0) (relu != 0) . keep / (1 - p) with keep = draws[i] >= p compared in fp32 (p = 0: draws may be NULL);
+ *   x == y is allowed.  The randomness is an input: nn.Dropout's distribution, not its generator stream.
+ * drc_act_bwd_rows: dz = dy . [y > 0] (relu != 0) . keep / (1 - p) on row-major [M][N]; db[N / fold] = column sums of dz, `fold`
+ *   neighbouring columns per entry, summed in fp64 in a fixed order (per-block partials in `scratch`, drc_act_bwd_rows_scratch_doubles(M, N)
+ *   doubles, added in block order by a second launch; no atomics).  db may be NULL (no scratch needed).
+ * drc_act_bwd_blocked: the same for the engine's blocked layout float[units][ceil(C/16)][H+2ph][W+2pw][16] (dy, y, dz of one geometry;
+ *   only the interior is read and written): dz = dy . [y > 0], db[ceil(C/16)*16] per-channel sums over all units and pixels. */
+int drc_linear_pack_cols(const float* a, int R, int K, float* out, void* stream);
+int drc_relu_dropout_fwd(const float* x, const float* draws, float* y, int64_t total, float p, int relu, void* stream);
+int64_t drc_act_bwd_rows_scratch_doubles(int M, int N);
+int drc_act_bwd_rows(const float* dy, const float* y, const float* draws, float p, int relu, int M, int N, int fold, float* dz, float* db,
+                     double* scratch, int64_t scratch_doubles, void* stream);
+int64_t drc_act_bwd_blocked_scratch_doubles(int units, int C, int H);
+int drc_act_bwd_blocked(const float* dy, const float* y, int relu, int units, int C, int H, int W, int ph, int pw, float* dz, float* db,
+                        double* scratch, int64_t scratch_doubles, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * a10. PSMLoss / EndPointErrorLoss (utils/loss_utils.py:9-32, utils/stereo_utils.py:185-208).
