@@ -57,6 +57,13 @@ class DrcFpnPyramid(C.Structure):
     _fields_ = [("feat", C.c_void_p * 8), ("H", C.c_int32 * 8), ("W", C.c_int32 * 8), ("scale", C.c_float * 8), ("n_levels", C.c_int32)]
 
 
+class DrcSrpnLevels(C.Structure):
+    _fields_ = [("n_levels", C.c_int32), ("N", C.c_int32), ("A", C.c_int32), ("C", C.c_int32), ("cap", C.c_int32), ("reserved", C.c_int32),
+                ("H", C.c_int32 * 8), ("W", C.c_int32 * 8), ("pix_off", C.c_int64 * 9),
+                ("left", C.c_void_p * 8), ("right", C.c_void_p * 8), ("hidden", C.c_void_p * 8), ("hidden_n_stride", C.c_int64 * 8),
+                ("glogits", C.c_void_p * 8), ("gbbox", C.c_void_p * 8)]
+
+
 class DrcWgradParams(C.Structure):
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("gw", C.c_void_p),
                 ("a_n_stride", C.c_int64), ("a_cb_stride", C.c_int64), ("a_d_stride", C.c_int64), ("a_h_stride", C.c_int64),
@@ -104,6 +111,9 @@ _SIGS = {
     "drc_act_bwd_blocked_scratch_doubles": (C.c_int64, [_I, _I, _I]),
     "drc_act_bwd_blocked": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, C.c_int64, _P]),
     "drc_roi_align_fpn_bwd": (_I, [C.POINTER(DrcFpnPyramid), _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "drc_srpn_active_pixels": (_I, [C.POINTER(DrcSrpnLevels), _P, _P, _P, _P, _P, _P]),
+    "drc_srpn_gather_rows": (_I, [C.POINTER(DrcSrpnLevels), _P, _P, _P, _P, _P, _P, _P]),
+    "drc_srpn_col2im": (_I, [C.POINTER(DrcSrpnLevels), _P, _P, _I, _P]),
     "drc_conv3d_k3_wino_rb_fwd": (_I, [C.POINTER(DrcTapconvParams), _P]),
     "drc_conv3d_k3_wino_rb_supported": (_I, [_I, _I, _I, _I]),
     "drc_conv2d_k3_wino_rb_supported": (_I, [_I, _I, _I]),

@@ -135,29 +135,36 @@ def balanced_sample(labels, cand_counts, batch, fraction, draws=None, want_indic
     return pos, neg, counts, idx
 
 
+def srpn_loss_launch(pos_mask, neg_mask, reg_targets, counts, beta, logits, bbox):
+    """One drc_det2d_srpn_loss_fwd launch over contiguous per-level maps -> (terms [3], [gradient per cls map], [gradient per bbox map])."""
+    L = len(logits)
+    dev = logits[0].device
+    N, A = logits[0].shape[0], logits[0].shape[1] // 2
+    glogits, gbbox = [torch.empty_like(m) for m in logits], [torch.empty_like(m) for m in bbox]
+    rows, off = [], 0
+    for z, b, gz, gb in zip(logits, bbox, glogits, gbbox):
+        H, W = z.shape[2:]
+        rows += [z.data_ptr(), b.data_ptr(), gz.data_ptr(), gb.data_ptr(), H, W, off]
+        off += H * W * A
+    table = (C.c_int64 * len(rows))(*rows)
+    lib = _lib.lib()
+    n_part = lib.drc_det2d_srpn_loss_partials(N, A, L, _host(table))
+    if n_part < 0:
+        raise RuntimeError("srpn_loss: unsupported shape")
+    partials = torch.empty(n_part, dtype=torch.float64, device=dev)
+    terms = torch.empty(3, dtype=torch.float32, device=dev)
+    st = lib.drc_det2d_srpn_loss_fwd(N, A, L, _host(table), off, E._ptr(pos_mask), E._ptr(neg_mask), E._ptr(reg_targets), E._ptr(counts),
+                                     float(beta), E._ptr(partials), E._ptr(terms), E._stream_ptr(dev))
+    _lib.check(st, "drc_det2d_srpn_loss_fwd")
+    return terms, glogits, gbbox
+
+
 class _SRPNLoss(Function):
     @staticmethod
     def forward(ctx, pos_mask, neg_mask, reg_targets, counts, beta, *maps):
         L = len(maps) // 2
         logits, bbox = [m.contiguous() for m in maps[:L]], [m.contiguous() for m in maps[L:]]
-        dev = logits[0].device
-        N, A = logits[0].shape[0], logits[0].shape[1] // 2
-        glogits, gbbox = [torch.empty_like(m) for m in logits], [torch.empty_like(m) for m in bbox]
-        rows, off = [], 0
-        for z, b, gz, gb in zip(logits, bbox, glogits, gbbox):
-            H, W = z.shape[2:]
-            rows += [z.data_ptr(), b.data_ptr(), gz.data_ptr(), gb.data_ptr(), H, W, off]
-            off += H * W * A
-        table = (C.c_int64 * len(rows))(*rows)
-        lib = _lib.lib()
-        n_part = lib.drc_det2d_srpn_loss_partials(N, A, L, _host(table))
-        if n_part < 0:
-            raise RuntimeError("srpn_loss: unsupported shape")
-        partials = torch.empty(n_part, dtype=torch.float64, device=dev)
-        terms = torch.empty(3, dtype=torch.float32, device=dev)
-        st = lib.drc_det2d_srpn_loss_fwd(N, A, L, _host(table), off, E._ptr(pos_mask), E._ptr(neg_mask), E._ptr(reg_targets), E._ptr(counts),
-                                         float(beta), E._ptr(partials), E._ptr(terms), E._stream_ptr(dev))
-        _lib.check(st, "drc_det2d_srpn_loss_fwd")
+        terms, glogits, gbbox = srpn_loss_launch(pos_mask, neg_mask, reg_targets, counts, beta, logits, bbox)
         ctx.grads = (glogits, gbbox)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(terms)

@@ -6,9 +6,13 @@ of generalized_rcnn.py:15-64) in its shipped stereo configuration (configs/kitti
 
 state_dict layout as in the reference: ``backbone.*``, ``rpn.*``, ``roi_heads.box.*``, ``roi_heads.mask.*`` (tests/test_detector2d.py
 checks the key sets of the heads against the reference's).  DISPNET_ON (the FPN-feature disparity head of the early fork, dispmodule.py)
-and DET3D_ON are separate models downstream and raise; training the whole 2D stage is not built (the shipped 3D configs freeze it:
-FIX_BACKBONE / FIX_RPN / FIX_BOX_HEAD) -- its ROI heads train on their own (roi_heads.StereoCombinedROIHeads), the trunk's backward, the
-Stereo RPN's training forward and the train-time proposal selection are missing."""
+and DET3D_ON are separate models downstream and raise.
+
+Training runs with the trunk frozen (the reference's SOLVER.FIX_BACKBONE): every backbone parameter has requires_grad False, the backbone
+runs in its eval form under no_grad (its range guard around the backbone only), and the Stereo RPN and the ROI heads train on its
+features: forward(lrimages, lrtargets) returns the merged loss dict (loss_classifier, loss_box_reg, loss_mask, loss_objectness,
+loss_rpn_box_reg).  A sub-module in eval mode contributes no losses (the reference's FIX_RPN / FIX_BOX_HEAD).  What is still missing
+for training the whole 2D stage: the trunk's backward only."""
 from types import SimpleNamespace
 
 import torch
@@ -30,7 +34,8 @@ def default_cfg_2d(conv_body="R-101-FPN", num_classes=2, post_nms_top_n_test=300
         RESNETS=SimpleNamespace(BACKBONE_OUT_CHANNELS=256, RES2_OUT_CHANNELS=256),
         RPN=SimpleNamespace(USE_FPN=True, ANCHOR_SIZES=(32, 64, 128, 256, 512), ANCHOR_STRIDE=(4, 8, 16, 32, 64), ASPECT_RATIOS=(0.5, 1.0, 2.0),
                             STRADDLE_THRESH=0, PRE_NMS_TOP_N_TEST=6000, POST_NMS_TOP_N_TEST=post_nms_top_n_test, NMS_THRESH=0.7, MIN_SIZE=0,
-                            FPN_POST_NMS_TOP_N_TEST=2000),
+                            FPN_POST_NMS_TOP_N_TEST=2000, FG_IOU_THRESHOLD=0.7, BG_IOU_THRESHOLD=0.3, BATCH_SIZE_PER_IMAGE=256,
+                            POSITIVE_FRACTION=0.5, PRE_NMS_TOP_N_TRAIN=2000, POST_NMS_TOP_N_TRAIN=2000, FPN_POST_NMS_TOP_N_TRAIN=2000),
         ROI_HEADS=SimpleNamespace(USE_FPN=True, BBOX_REG_WEIGHTS=(10.0, 10.0, 5.0, 5.0), SCORE_THRESH=0.05, NMS=0.5, DETECTIONS_PER_IMG=100,
                                   FG_IOU_THRESHOLD=0.5, BG_IOU_THRESHOLD=0.5, BATCH_SIZE_PER_IMAGE=512, POSITIVE_FRACTION=0.25),
         ROI_BOX_HEAD=SimpleNamespace(POOLER_RESOLUTION=7, POOLER_SCALES=scales, POOLER_SAMPLING_RATIO=0,
@@ -52,11 +57,17 @@ class DispRCNN(nn.Module):
         self.rpn = build_stereorpn(cfg, self.backbone.out_channels)
         self.roi_heads = build_roi_heads(cfg, self.backbone.out_channels)
 
-    def forward(self, lrimages, lrtargets=None):
+    def forward(self, lrimages, lrtargets=None, draws=None):
+        """draws (training): optionally {'rpn_sample', 'sample', 'dropout'} -- the randomness of the RPN's sampler and of the box head
+        (StereoRPN.forward, ROIBoxHead), so that a step can be repeated."""
         if self.training:
-            raise NotImplementedError("training the whole 2D stage is not built: the ROI heads train (StereoCombinedROIHeads), the trunk's "
-                                      "backward, the Stereo RPN's training forward and the train-time proposal selection are missing "
-                                      "(the shipped disparity / 3D configs freeze the stage)")
+            if any(p.requires_grad for p in self.backbone.parameters()):
+                raise NotImplementedError("training the 2D stage with a trainable backbone is not built: the trunk's backward is missing; freeze "
+                                          "the backbone's parameters (the reference's SOLVER.FIX_BACKBONE; the shipped disparity / 3D "
+                                          "configs freeze the whole stage)")
+            if lrtargets is None:
+                raise ValueError("In training mode, targets should be passed")
+            return self._forward_train(lrimages, lrtargets, draws)
         left_images, right_images = to_image_list(lrimages["left"]), to_image_list(lrimages["right"])
         # the split-f16 layers of the trunk and of the RPN head report to ONE range guard, read once at the end of the stage; an overflow
         # (|v| > 65504: the fp32 reference has no such limit) repeats the stage on the fp32 kernels (engine.guarded)
@@ -68,13 +79,50 @@ class DispRCNN(nn.Module):
                              enabled=bool(getattr(self, "overflow_check", True)))
         return self._forward_once(left_images, right_images)
 
-    def _forward_once(self, left_images, right_images):
+    def _features(self, left_images, right_images):
         n = left_images.tensors.shape[0]
         feats = self.backbone(torch.cat((left_images.tensors, right_images.tensors), dim=0))
         left_features, right_features = [f[:n] for f in feats], [f[n:] for f in feats]
         rt = getattr(self.backbone, "_rt", None)
         # the blocked pyramid behind THESE dense maps (None if another forward of the backbone has overwritten the workspace since)
         levels = rt.blocked_levels(feats) if rt is not None and hasattr(rt, "blocked_levels") else None
+        return left_features, right_features, levels
+
+    def _forward_once(self, left_images, right_images):
+        left_features, right_features, levels = self._features(left_images, right_images)
         left_prop, right_prop, _ = self.rpn(left_images, right_images, left_features, right_features, blocked_levels=levels)
         _, left_result, right_result, _ = self.roi_heads(left_features, right_features, left_prop, right_prop)
         return {"left": left_result, "right": right_result}
+
+    def frozen_features(self, left_images, right_images):
+        """The frozen trunk's pyramids for a training step: the backbone in its eval form under no_grad, its split-f16 layers inside a
+        range guard of their own (an overflow repeats the backbone on the fp32 kernels).  -> (left maps, right maps, blocked levels)."""
+        from ... import engine as E
+        was_training = self.backbone.training
+        self.backbone.eval()
+        try:
+            with torch.no_grad():
+                if left_images.tensors.is_cuda:
+                    if getattr(self, "_guard", None) is None:
+                        self._guard = E.OverflowGuard(left_images.tensors.device)
+                    return E.guarded(self._guard, lambda: self._features(left_images, right_images), what="DispRCNN backbone (split-f16 3x3 layers)",
+                                     enabled=bool(getattr(self, "overflow_check", True)))
+                return self._features(left_images, right_images)
+        finally:
+            self.backbone.train(was_training)
+
+    def _forward_train(self, lrimages, lrtargets, draws):
+        draws = draws or {}
+        left_images, right_images = to_image_list(lrimages["left"]), to_image_list(lrimages["right"])
+        left_targets, right_targets = lrtargets["left"], lrtargets["right"]
+        left_features, right_features, levels = self.frozen_features(left_images, right_images)
+        left_prop, right_prop, proposal_losses = self.rpn(left_images, right_images, left_features, right_features, left_targets, right_targets,
+                                                          blocked_levels=levels, draws=draws.get("rpn_sample"))
+        head_draws = {k: draws[k] for k in ("sample", "dropout") if k in draws} or None
+        _, _, _, detector_losses = self.roi_heads(left_features, right_features, left_prop, right_prop, left_targets, right_targets, draws=head_draws)
+        losses = {}
+        solver = getattr(self.cfg, "SOLVER", None)
+        if solver is None or getattr(solver, "TRAIN_2D", True):
+            losses.update(detector_losses)
+            losses.update(proposal_losses)
+        return losses

@@ -661,6 +661,39 @@ int drc_tapconv_wgrad(const drc_wgrad_params* p, void* stream);
 int drc_bilinear_up_blocked_bwd(const float* grad_y, const int* geom_y, float* grad_x, const int* geom_x, void* stream);
 int drc_avgpool2d_blocked_bwd(const float* grad_y, const int* geom_y, float* grad_x, const int* geom_x, int k, void* stream);
 
+/* ---- The Stereo RPN's sparse head backward (csrc/srpn_train.hip) --------------------------------------------------------------
+ * The RPN loss touches at most `cap` anchors per image, and the pair softmax couples only channels of one pixel, so the gradient of the
+ * head maps is zero outside at most `cap` pixels per image.  A pixel of an image is addressed by q = pix_off[level] + y * W + x
+ * (levels concatenated); the images' anchors are level-major, then (y * W + x) * A + a, so anchor q * A + a sits on pixel q.  Every
+ * buffer has N * cap rows, row img * cap + k is the k-th active pixel of image img in ascending q; rows past an image's count are zero
+ * rows.  Nothing is read back to the host and nothing is added atomically: the same bits run to run. */
+#define DRC_SRPN_MAX_LEVELS 8
+typedef struct drc_srpn_levels {
+    int32_t n_levels, N, A, C;                  /* images, anchors per pixel, channels of a feature map */
+    int32_t cap, reserved;
+    int32_t H[DRC_SRPN_MAX_LEVELS], W[DRC_SRPN_MAX_LEVELS];
+    int64_t pix_off[DRC_SRPN_MAX_LEVELS + 1];   /* pixel offset of each level within an image; [n_levels] = pixels per image */
+    const float* left[DRC_SRPN_MAX_LEVELS];     /* dense [N,C,H,W] feature maps (gather: read; col2im: the gradient maps, written) */
+    const float* right[DRC_SRPN_MAX_LEVELS];
+    const float* hidden[DRC_SRPN_MAX_LEVELS];   /* blocked [N][4C/16][H][W][16] hidden maps, no halo: left blocks, then right blocks */
+    int64_t hidden_n_stride[DRC_SRPN_MAX_LEVELS];
+    const float* glogits[DRC_SRPN_MAX_LEVELS];  /* dense [N,2A,H,W] / [N,6A,H,W]: the loss's gradient maps */
+    const float* gbbox[DRC_SRPN_MAX_LEVELS];
+} drc_srpn_levels;
+/* drc_srpn_active_pixels: pos | neg [N * P * A] uint8 -> row_pix [N * cap] int32 (q of each row, -1 past the count), counts [N] int32,
+ *   index [N * P] int32 laid out level-major ([N,H,W] of level l at N * pix_off[l]): the row of each pixel or -1, written completely.
+ *   Several sampled anchors on one pixel give one row; active pixels beyond `cap` of an image (the sampler never makes them) are dropped.
+ * drc_srpn_gather_rows: per row, T [N*cap, 4C] from the hidden maps, Xcol [2*N*cap, 9C] (left patches, then right; column
+ *   (c, ky, kx), zeros outside the map) from the feature maps, G [N*cap, 8A] from the gradient maps, the 2A logit channels scaled by
+ *   *g_obj and the 6A box channels by *g_box (device scalars; NULL = 0).  Each of T, Xcol, G may be NULL (not gathered).
+ * drc_srpn_col2im: dXcol [2*N*cap, 9C] + index -> every element of lv->left[l] / lv->right[l] (written, zeros included): each element
+ *   sums, in tap order (ky, kx), the at most nine taps whose neighbouring pixel is active.  view_mask: bit 0 left, bit 1 right. */
+int drc_srpn_active_pixels(const drc_srpn_levels* lv, const uint8_t* pos, const uint8_t* neg, int32_t* row_pix, int32_t* counts,
+                           int32_t* index, void* stream);
+int drc_srpn_gather_rows(const drc_srpn_levels* lv, const int32_t* row_pix, const float* g_obj, const float* g_box, float* T, float* Xcol,
+                         float* G, void* stream);
+int drc_srpn_col2im(const drc_srpn_levels* lv, const float* dxcol, const int32_t* index, int view_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
