@@ -175,6 +175,7 @@ _SIGS = {
     "drc_rs16_to_blocked": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "drc_head_gather_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, C.c_float, _P]),
     "drc_head_gather_rows_fwd": (_I, [_P, _P, _P, C.c_float, C.c_float, C.c_float, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "drc_head_gather_planar_fwd": (_I, [_P, _P, _P, C.c_float, C.c_float, C.c_float, _I, _P, _P, _I, _I, _I, _I, _P]),
     "drc_conv2d_k3_s16_supported": (_I, [_I, _I, _I, _I, _I]),
     "drc_conv2d_k3_s16_fwd": (_I, [C.POINTER(DrcS16ConvParams), _P]),
     "drc_deconv3d_k3s2_direct_s16_fwd": (_I, [C.POINTER(DrcTapconvParams), _P, _P, _P]),

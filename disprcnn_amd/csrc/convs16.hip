@@ -1,3 +1,4 @@
+#ifndef CONVS16_KERNEL      // (first pass; see the second one behind the kernel template)
 // convs16.hip -- 3x3x3 stride-1 convolution (+BN, +residual, +ReLU) in SPLIT-f16 arithmetic on the f16 matrix cores (gfx950 / CDNA4), round 5.
 //
 //   reference arithmetic: convbn_3d k3 s1 p1 of stackhourglass.py:7-51,63-88 (dres0 / dres1 / classif[0], hourglass conv2 / conv4) and, fused
@@ -60,6 +61,8 @@ namespace {
 constexpr int PV_ROWS = 128;    // voxels per chunk plane of a slab (>= (rows + 2) * SX + the 4 columns lanes 28..31 over-read)
 constexpr int PV_FLAT = 192;    // ... of the flat form on 28-column maps (7 stacked rows, the last one up to column 8)
 constexpr int RING = 3;
+#define CONVS16_KERNEL convs16_kernel
+#endif
 
 // RT rows x WT columns of the map make one 32-voxel MFMA tile: 1 x 28 (full-resolution maps, tiles along x), 2 x 14 and 4 x 7 (the
 // hourglass' half- and quarter-resolution maps: 28 of 32 lanes busy there as well).
@@ -85,8 +88,8 @@ constexpr int RING = 3;
 // same instructions -- the sums are always computed, the layout selects the data and the offsets of the same two stores (the second one
 // is dropped by its offset in the rows layout).  drc_head_gather_rows_fwd adds T0[y-1] + (T1a[y] + T1b[y]) + T2[y+1] of the same column:
 // 16 B written + 16 read per voxel.
-// FLAT, written RT == 0 (the plain and the residual 32 -> 32 layer on 28-column maps: KW == 2, WT == 28, no Y32, no HEAD; the 64 -> 64
-// form on 14-column maps is described behind this paragraph): a tile is not an
+// FLAT, written RT == 0 (the plain and the residual 32 -> 32 layer on 28-column maps: KW == 2, WT == 28, no Y32; its HEAD form and the
+// 64 -> 64 form on 14-column maps are described behind this paragraph): a tile is not an
 // image row but 32 CONSECUTIVE voxels of the flattened (unit, row, x) order of a group of G units (p.dil bit 0x4000: G = 1, else 4), so all 32
 // MFMA columns of a tile work: 24.5 instead of 28 tiles per 28 x 28 plane.  Column c of a group = tiles 2c (wave pair r = 0) and 2c + 1: 64
 // voxels f = 64c .. 64c + 63, f = (n - n0) H W + y W + x; voxels past the group's last unit are masked like the ragged tiles of the row form.
@@ -98,6 +101,14 @@ constexpr int RING = 3;
 // read up to column 8 (voxel 188); H == 1 | 2 reach 9 | 8 rows only for a column that starts in the last 7 voxels of a row, and a column
 // starts at a multiple of 64 voxels of a group of 28 | 56 | 112 | 224: x = 0, 8, 16, 24 (two units: 7 rows).  Staging and store offsets are
 // relative to the column's first unit (at most 3 units further: 32 bits).
+// FLAT HEAD (p.head_rows == DRC_HEAD_PLANAR; the kernel is named convs16_headflat_kernel, below): the head arithmetic above on flat tiles.  A column is still a fixed set of voxels walked
+// through the depth, so w1h / w1l, head_mfma, pkeep / pbuf / pin and head_update with SC / SB are the row form's; only the store differs.  A flat
+// tile is no image row, so the width taps cannot be summed across lanes: the nine depth-summed sums are stored per SOURCE voxel in PLANES,
+// float [N][D][9][H W], plane j = kh*3 + kw, element y W + x -- lane half 0 stores j = 0..4, half 1 j = 5..8 (its fifth store dropped by its
+// offset, so both halves issue five dword stores: NS = 5), each store of a half 32 consecutive floats = one 128-byte segment; no DPP, no
+// permlane, no select on the layout.  The offsets are those of the lane's own voxel (du, y, x of ctx_of), relative to the column's first unit
+// like the RS16 stores, so a tile across a unit seam lands in two units' planes.  drc_head_gather_planar_fwd (s16_ops.hip) forms the width and
+// row sums of the rows layout in the rows layout's order: the same bits.
 // FLAT, KW == 4, WT == 14 (the plain and the residual 64 -> 64 layer on 14-column maps, conv2 of the hourglasses, whose row tiles are
 // 2 x 14): all four waves split K, so a workgroup has ONE tile and a column is 32 consecutive voxels f = 32c .. 32c + 31 of a group of G units
 // (dil bit 0x4000: G = 1, 0x8000: 8, else 4; the host sets exactly one).  Everything above holds with 32 for 64: two channel blocks are staged
@@ -106,7 +117,7 @@ constexpr int RING = 3;
 // refuses the form where one would need a ninth row or a fourth unit behind its first (s16_flat_half_fits).  The epilogue stores half a chunk
 // per wave, the row form's KW == 4 rule.  LDS 3 x 32 + 32 KB and 8 LDS-DMA instructions per wave and slab, as the row form.
 template <int KW, bool CV, int RT_ = 1, int WT = 28, bool RES = false, bool Y32 = false, bool HEAD = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void convs16_kernel(const drc_s16conv_params p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void CONVS16_KERNEL(const drc_s16conv_params p) {
     constexpr bool FL = RT_ == 0;               // flat tiles: no rows of the map, 32 consecutive voxels
     constexpr int RT = FL ? 1 : RT_;
     static_assert(!HEAD || (KW == 2 && !CV && RT == 1 && !RES && !Y32), "the fused cout-1 head is a form of the 32 -> 32 full-resolution layer");
@@ -122,7 +133,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     constexpr int CBI = KW / 2;                 // 32-channel input blocks
     constexpr int SROWS = RPW * RT + 2;
     static_assert(RT * WT <= 32, "tile shape");
-    static_assert(!FL || (((KW == 2 && WT == 28) || (KW == 4 && WT == 14)) && !CV && !Y32 && !HEAD), "flat tiles: the plain / residual 32 -> 32 layer on 28-column maps, 64 -> 64 on 14-column maps");
+    static_assert(!FL || (((KW == 2 && WT == 28) || (KW == 4 && WT == 14 && !HEAD)) && !CV && !Y32), "flat tiles: the plain / residual / head 32 -> 32 layer on 28-column maps, 64 -> 64 on 14-column maps");
     constexpr int FV = 32 * RPW;                // flat: voxels per column (one tile per wave set)
     constexpr int PV = FL && KW == 2 ? PV_FLAT : PV_ROWS;  // voxels per chunk plane (flat, 14-column maps: 8 stacked rows of 16 fit the row form's plane)
     constexpr int CPB = PV * 16;                // bytes per chunk plane
@@ -132,7 +143,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     constexpr int OWN = 16 / KW;                // accumulator registers (couts per lane) a wave finishes
     constexpr int XW = 4096;                    // bytes a wave publishes per plane: its 16 accumulator registers
     constexpr int NR = RES ? 2 : 0;             // residual loads per step (hi, lo)
-    constexpr int NS = 2;                       // stores per step (RS16 hi, lo | blocked fp32 x2)
+    constexpr bool HP = FL && HEAD;             // the flat head: planar partial sums, five dword stores per step
+    constexpr int NS = HP ? 5 : 2;              // stores per step (RS16 hi, lo | blocked fp32 x2 | head slot + fifth value | flat head: planes j = 5g .. 5g + 4)
     static_assert(!(Y32 && (KW != 2 || RES)), "the blocked fp32 output exists for the 32-channel layers without residual");
     static_assert(FL || (RT == 1 ? SROWS * SX + 4 <= PV : (SROWS + 1) * SX + 4 <= PV), "slab plane too small (incl. the rows / columns the idle lanes over-read)");
     char* ring = lds;
@@ -308,7 +320,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // output context of a column: unit bases + this lane's voxel offsets (plane 0, padded coordinates + 1)
     const bool hrows = HEAD && p.head_rows;                                         // the rows layout: float [N][D][H][W][4]
     const int hs_slotB = hrows ? 16 : 48;
-    const long hs_planeB = (long)H * W * hs_slotB, hs_nB = (long)D * hs_planeB;    // HEAD: float [N][D][H][W][12]
+    const long hs_planeB = HP ? (long)HW * 36 : (long)H * W * hs_slotB, hs_nB = (long)D * hs_planeB;    // HEAD: float [N][D][H][W][12]; flat: float [N][D][9][H W]
+    const unsigned hs_jB = (unsigned)HW * 4u;                                      // flat head: bytes of one of the nine planes of a depth plane
     const bool hs_drop0 = hrows && g, hs_drop1 = hrows || g;                        // lanes whose first / second store is dropped by its offset
     struct Ctx { char* y16b; char* y32b; const char* resb; char* hsb; unsigned o16, o32, ohs, bf; bool ok; };
     auto ctx_of = [&](const Col& c) __attribute__((always_inline)) {
@@ -317,10 +330,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if constexpr (FL) {
             // this lane's voxel: number 32 r + n_ of the column (KW == 4: r == 0), du units behind the column's first one; a lane past the group's end is masked
             // and reads (never stores) the slab's first voxel
-            q.hsb = (char*)p.w;
+            q.hsb = HEAD ? (char*)p.head + (long)c.n * hs_nB : (char*)p.w;
             q.y32b = (char*)p.w;
             q.ohs = q.o32 = 0u;
-            q.y16b = (char*)p.y16 + (long)c.n * ynB;
+            q.y16b = HEAD ? (char*)p.w : (char*)p.y16 + (long)c.n * ynB;
             q.resb = p.res ? (const char*)p.res + (long)c.n * ynB : (const char*)p.w;
             q.ok = r * 32 + n_ < c.lim;
             const int e0 = q.ok ? c.rem0 + r * 32 + n_ : c.rem0;
@@ -331,6 +344,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             // (the row form's rule: KW == 2 a whole chunk per wave, KW == 4 half a chunk)
             const int och = KW == 2 ? k * 2 + g : (k >> 1) * 2 + g, ohalf = KW == 2 ? 0 : (k & 1) * 8;
             q.o16 = (unsigned)((long)du * ynB + (long)ct * xcbB + planeB + (long)(yl + 1) * rowB + (long)och * (Wp * 16) + (long)(xv + 1) * 16 + ohalf);
+            // flat head: element y W + x of plane j = 5g of the lane's own voxel (planes 5g + 1 .. at + hs_jB each), relative to the column's first unit
+            if constexpr (HEAD) q.ohs = (unsigned)((long)du * hs_nB + (long)(5 * g) * hs_jB + (long)e * 4);
             return q;
         }
         q.hsb = HEAD ? (char*)p.head + (long)c.n * hs_nB : (char*)p.w;
@@ -562,8 +577,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 const __amdgpu_buffer_rsrc_t hsr = __builtin_amdgcn_make_buffer_rsrc(scur ? cx_cur.hsb : cx_prev.hsb, 0, 0x7FFFFF00, 0x00020000);
                 const unsigned oh_ = scur ? cx_cur.ohs : cx_prev.ohs;
                 const unsigned po = ok_ ? (unsigned)((long)ps * hs_planeB) : 0x80000000u;
-                __builtin_amdgcn_raw_buffer_store_b128(head_pack(o_), hsr, oh_ + (hs_drop0 ? 0x80000000u : po), 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o_[4]), hsr, oh_ + 16 + (hs_drop1 ? 0x80000000u : po), 0, 0);
+                if constexpr (HP) {
+                    // planar: one dword per (kh, kw) plane, 32 consecutive floats per lane half; half 1 has no fifth plane (dropped by its offset)
+#pragma unroll
+                    for (int j = 0; j < 5; ++j)
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o_[j]), hsr, oh_ + (unsigned)j * hs_jB + (j == 4 && g ? 0x80000000u : po), 0, 0);
+                } else {
+                    __builtin_amdgcn_raw_buffer_store_b128(head_pack(o_), hsr, oh_ + (hs_drop0 ? 0x80000000u : po), 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o_[4]), hsr, oh_ + 16 + (hs_drop1 ? 0x80000000u : po), 0, 0);
+                }
             }
         };
         auto head_mfma = [&](int i) __attribute__((always_inline)) {
@@ -688,11 +710,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const bool ok_ = k == 0 && cx_cur.ok;
         const __amdgpu_buffer_rsrc_t hsr = __builtin_amdgcn_make_buffer_rsrc(cx_cur.hsb, 0, 0x7FFFFF00, 0x00020000);
         const unsigned po = ok_ ? (unsigned)((long)(D - 1) * hs_planeB) : 0x80000000u;
-        __builtin_amdgcn_raw_buffer_store_b128(head_pack(SC), hsr, cx_cur.ohs + (hs_drop0 ? 0x80000000u : po), 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, SC[4]), hsr, cx_cur.ohs + 16 + (hs_drop1 ? 0x80000000u : po), 0, 0);
+        if constexpr (HP) {
+#pragma unroll
+            for (int j = 0; j < 5; ++j)
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, SC[j]), hsr, cx_cur.ohs + (unsigned)j * hs_jB + (j == 4 && g ? 0x80000000u : po), 0, 0);
+        } else {
+            __builtin_amdgcn_raw_buffer_store_b128(head_pack(SC), hsr, cx_cur.ohs + (hs_drop0 ? 0x80000000u : po), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, SC[4]), hsr, cx_cur.ohs + 16 + (hs_drop1 ? 0x80000000u : po), 0, 0);
+        }
     }
     og.flush(p.ovf);
 }
+
+// The flat head runs this body under a name of its own, convs16_headflat_kernel<2,false,0,28,false,false,true>: the row head
+// stays the ONE fused-head instantiation of convs16_kernel that tests/test_isa_weights_in_agprs.py counts (tests/test_isa_head_flat.py holds
+// the new kernel to the same caps).  A shared __device__ body behind two __global__ wrappers would do as well, but it changes the scalar
+// register allocation of the other nineteen instantiations (tools/isa_step_stats.py: SGPR spills, lane moves); so the template above is
+// compiled a second time, textually: this file includes itself once, and the second pass sees nothing but the template.
+#ifndef CONVS16_SECOND_PASS
+#define CONVS16_SECOND_PASS
+#undef CONVS16_KERNEL
+#define CONVS16_KERNEL convs16_headflat_kernel
+#include "convs16.hip"
+#undef CONVS16_KERNEL
 
 constexpr long FLAT_MIN_COLUMNS = 2048;       // below: the row form (eight columns per workgroup; 256 Config-A ROIs have 3136)
 constexpr long FLAT_HALF_GROUP = 8;           // the 64 -> 64 form on 14-column maps: units per group where the caller names none
@@ -739,8 +779,12 @@ int launch2(const drc_s16conv_params& p, hipStream_t stream) {
     constexpr size_t lds = CV ? (size_t)s16cv::LDS_BYTES : RING * SLAB + 2 * 4 * XW + (HEAD ? 2 * 2 * XW : 0);
     static_assert(lds <= 160 * 1024, "LDS");
     static bool attr_done = false;
+    void (*const kern)(const drc_s16conv_params) = [] {
+        if constexpr (FLAT && HEAD) return convs16_headflat_kernel<KW, CV, RT, WT, RES, Y32, HEAD>;
+        else return convs16_kernel<KW, CV, RT, WT, RES, Y32, HEAD>;
+    }();
     if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)convs16_kernel<KW, CV, RT, WT, RES, Y32, HEAD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_done = true;
     }
     constexpr int rows = FLAT ? 1 : (4 / KW) * RT;
@@ -750,7 +794,7 @@ int launch2(const drc_s16conv_params& p, hipStream_t stream) {
     long blocks = 256;                                   // column workers x cout tiles (the tiles of a worker side by side on its XCD)
     while (blocks > 8 * n_ct && blocks / (2 * n_ct) >= columns) blocks /= 2;
     if constexpr (CV) blocks = s16cv::s16_cvrows_blocks<1>(p);      // (its work items are rows, not columns of rows)
-    hipLaunchKernelGGL((convs16_kernel<KW, CV, RT, WT, RES, Y32, HEAD>), dim3((unsigned)blocks), dim3(256), lds, stream, p);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, stream, p);
     return (int)hipGetLastError();
 }
 
@@ -790,7 +834,11 @@ extern "C" int drc_conv3d_k3_s16_flat(const drc_s16conv_params* pp) {
     const long unit16 = (long)(p.D + 2) * (p.H + 2) * (p.W + 2) * 128;
     const bool half = p.cin == 64 && p.cout == 64 && p.W == 14;
     const bool shape = (p.cin == 32 && p.cout == 32 && p.W == 28) || half;
-    const bool can = shape && p.D > 0 && p.H > 0 && p.N > 0 && p.x && p.y16 && !p.y32 && !p.head && !p.left && !p.right &&
+    // the fused head has the form where the caller asks for the planar layout of its partial sums (head_rows == DRC_HEAD_PLANAR: the only
+    // layout a tile that is no image row can write); the head's depth rule (D >= 6, D % 3 == 0) and four units' planes inside 32 bits
+    const bool hp = p.head && p.head_rows == DRC_HEAD_PLANAR;
+    const bool out = hp ? !p.y16 && !p.res && !half && p.D >= 6 && p.D % 3 == 0 && 4L * p.D * p.H * p.W * 36 < 0x7FFFFF00L : p.y16 && !p.head;
+    const bool can = shape && p.D > 0 && p.H > 0 && p.N > 0 && p.x && out && !p.y32 && !p.left && !p.right &&
                      4 * (p.cout / 32) * unit16 < 0x7FFFFF00L && (!half || s16_flat_half_fits(p.N, s16_flat_group(p), p.H));
     if (p.dil & 0x1000) return forced ? -1 : 0;
     if (!can) return forced ? -4 : 0;
@@ -806,7 +854,8 @@ extern "C" int drc_conv3d_k3_s16_fwd(const drc_s16conv_params* pp, void* stream)
     if (p.head) {                                                                   // fused cout-1 head: no tensor output, 32 -> 32 at full resolution
         if (!p.w1 || p.y16 || p.y32 || p.res || cv) return -1;
         if (p.cin != 32 || p.cout != 32 || p.W % 28 || p.D < 6 || p.D % 3) return -4;      // (the depth sums of the head close over real planes only)
-        if (p.head_rows && p.W != 28) return -4;                                    // the rows layout: one x tile per row
+        if (p.head_rows < 0 || p.head_rows > DRC_HEAD_PLANAR) return -1;
+        if (p.head_rows && p.W != 28) return -4;                                    // the rows layout: one x tile per row; planar: the flat form's maps
         if ((long)p.D * p.H * p.W * 48 >= 0x7FFFFF00L) return -5;
     } else if (p.head_rows) return -1;
     else if (!p.y16 == !p.y32) return -1;                                         // exactly one output
@@ -823,11 +872,19 @@ extern "C" int drc_conv3d_k3_s16_fwd(const drc_s16conv_params* pp, void* stream)
     hipStream_t s = (hipStream_t)stream;
     if (drc_conv3d_k3_s16_wide(pp)) return drc_conv3d_k3_s16_wide_fwd(pp, stream);      // the cost-volume form at large batches: two tiles per wave (convs16w.hip)
     if (cv) return launch<4, true>(p, s);
-    const int flat = drc_conv3d_k3_s16_flat(pp);
+    int flat = drc_conv3d_k3_s16_flat(pp);
+    if (p.head && p.head_rows == DRC_HEAD_PLANAR && flat == 0) {
+        // the layout is the caller's word: a planar head IS the flat form, whatever the launch's size (the caller asks drc_conv3d_k3_s16_flat
+        // first where it wants the library's choice); no such form for this block: -4
+        drc_s16conv_params f = p;
+        f.dil = (p.dil & ~0x1000) | 0x2000;
+        flat = drc_conv3d_k3_s16_flat(&f);
+    }
     if (flat < 0) return flat;
     if (flat) {
         drc_s16conv_params q = p;                   // the kernel reads the group size from the bits alone
         q.dil = (p.dil & ~0x1C000) | (flat == 1 ? 0x4000 : flat == 8 ? 0x8000 : 0x10000);
+        if (p.head) return launch2<2, false, 0, 28, false, false, true>(q, s);
         if (p.cin == 64) return p.res ? launch2<4, false, 0, 14, true, false>(q, s) : launch2<4, false, 0, 14, false, false>(q, s);
         return p.res ? launch2<2, false, 0, 28, true, false>(q, s) : launch2<2, false, 0, 28, false, false>(q, s);
     }
@@ -835,3 +892,4 @@ extern "C" int drc_conv3d_k3_s16_fwd(const drc_s16conv_params* pp, void* stream)
     if (p.W <= 14) return p.cin == 32 ? launch<2, false, 2, 14>(p, s) : launch<4, false, 2, 14>(p, s);
     return p.cin == 32 ? launch<2, false>(p, s) : launch<4, false>(p, s);
 }
+#endif  // CONVS16_SECOND_PASS

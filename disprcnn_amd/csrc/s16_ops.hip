@@ -329,7 +329,69 @@ __global__ __launch_bounds__(256) void head_gather_rows_kernel(const HeadRows hr
         }
     }
 }
+// ---- the planar layout of the flat fused heads (convs16.hip, head_rows == DRC_HEAD_PLANAR): float [N][D][9][H W], plane j = kh*3 + kw of the
+// nine depth-summed partial sums per SOURCE voxel.  The width sums the rows layout forms in the conv kernel are formed here, in the same
+// order -- T0 = (S0[x-1] + S1[x]) + S2[x+1], T1a = S3[x-1] + S4[x], T1b = S5[x+1], T2 = (S6[x-1] + S7[x]) + S8[x+1], a neighbour outside
+// [0, W) entering as the operand +0.0f (the add is performed, as the DPP shift's zero is) -- and then the rows gather's own expression.
+// One thread per OUTPUT voxel: it reads the nine S values its sum is made of -- S0..S2 of the row above at x - 1 | x | x + 1, S3..S5 of its
+// own row, S6..S8 of the row below -- so every S value is read by exactly one thread, and consecutive lanes read consecutive floats of a
+// plane (784 contiguous floats at 28 x 28; the row walk of the rows gather would read 112-byte pieces here).  No LDS, no halo, 9 NH
+// independent loads in flight per thread.  A row outside [0, H) is never read: above, the rows gather's `up` is the constant 0.f (the add
+// is performed); below, the add is skipped.
+template <int NH>
+__global__ __launch_bounds__(256) void head_gather_planar_kernel(const HeadRows hr, const float* __restrict__ res, float* __restrict__ cost, long total, int H, int W) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long HW = (long)H * W;
+    const long plane = i / HW;                                      // n * D + z
+    const int e = (int)(i - plane * HW);
+    const int y = e / W, x = e - y * W;
+    const bool xm = x > 0, xp = x + 1 < W, ym = y > 0, yp = y + 1 < H;
+    const int dm = xm ? -1 : 0, dp = xp ? 1 : 0, du = ym ? -W : 0, dd = yp ? W : 0;     // (clamped: a neighbour outside the plane is never read)
+    float v[NH][9];
+#pragma unroll
+    for (int k = 0; k < NH; ++k) {
+        const float* p = hr.rows[k] + plane * 9 * HW + e;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) v[k][j] = p[j * HW + (j < 3 ? du : j < 6 ? 0 : dd) + (j % 3 == 0 ? dm : j % 3 == 2 ? dp : 0)];
+    }
+    float c = res ? res[i] : 0.f;
+#pragma unroll
+    for (int k = 0; k < NH; ++k) {
+        const float* q = v[k];
+        const float l0 = xm ? q[0] : 0.f, l3 = xm ? q[3] : 0.f, l6 = xm ? q[6] : 0.f;
+        const float r2 = xp ? q[2] : 0.f, r5 = xp ? q[5] : 0.f, r8 = xp ? q[8] : 0.f;
+        const float t0 = (l0 + q[1]) + r2;
+        const float t1a = l3 + q[4];
+        const float t1b = r5;
+        const float t2 = (l6 + q[7]) + r8;
+        float s = (ym ? t0 : 0.f) + (t1a + t1b);                    // (y == 0: the rows gather's up = 0, the skipped row)
+        if (yp) s += t2;
+        c = hr.scale[k] * s + c;
+    }
+    cost[i] = c;
+}
 }  // namespace
+
+extern "C" int drc_head_gather_planar_fwd(const float* s0, const float* s1, const float* s2, float scale0, float scale1, float scale2, int nheads,
+                                          const float* res, float* cost, int N, int D, int H, int W, void* stream) {
+    if (nheads < 1 || nheads > 3) return -2;
+    const HeadRows hr = {{s0, s1, s2}, {scale0, scale1, scale2}};
+    for (int k = 0; k < nheads; ++k)
+        if (!hr.rows[k] || ((uintptr_t)hr.rows[k] & 3)) return -1;
+    if (!cost) return -1;
+    if (N < 0 || D <= 0 || H <= 0 || W <= 0) return -2;
+    if (N == 0) return 0;
+    const long cols = (long)N * D * H * W;
+    const long blocks = (cols + 255) / 256;
+    if (blocks > 0x7fffffffL) return -3;
+    const dim3 g((unsigned)blocks), b(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (nheads == 1) hipLaunchKernelGGL(head_gather_planar_kernel<1>, g, b, 0, s, hr, res, cost, cols, H, W);
+    else if (nheads == 2) hipLaunchKernelGGL(head_gather_planar_kernel<2>, g, b, 0, s, hr, res, cost, cols, H, W);
+    else hipLaunchKernelGGL(head_gather_planar_kernel<3>, g, b, 0, s, hr, res, cost, cols, H, W);
+    return (int)hipGetLastError();
+}
 
 extern "C" int drc_head_gather_rows_fwd(const float* rows0, const float* rows1, const float* rows2, float scale0, float scale1, float scale2, int nheads,
                                         const float* res, float* cost, int N, int D, int H, int W, void* stream) {

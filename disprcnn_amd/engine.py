@@ -957,6 +957,23 @@ def head_gather_rows(rows, scales, res, out):
     _lib.check(st, "drc_head_gather_rows_fwd")
 
 
+def head_gather_planar(planes, scales, res, out):
+    """head_gather_rows for heads in the planar layout (ConvPlanS16.run(head=..., head_layout=HEAD_PLANAR)): planes = fp32 buffers
+    [N][D][9][H*W]; the width sums are formed here, in the rows layout's order -- bit-identical to it."""
+    N, D, H, W = out.shape
+    if not 1 <= len(planes) <= 3 or len(scales) != len(planes):
+        raise ValueError("head_gather_planar: 1 to 3 heads, one scale each")
+    for r in planes:
+        if r.dtype != torch.float32 or r.numel() < N * D * H * W * 9 or not r.is_contiguous():
+            raise ValueError("head_gather_planar: planes = contiguous fp32 buffers of N*D*9*H*W")
+    if out.dtype != torch.float32 or not out.is_contiguous() or (res is not None and (res.dtype != torch.float32 or res.shape != out.shape or not res.is_contiguous())):
+        raise ValueError("head_gather_planar: out / res = contiguous fp32 [N,D,H,W]")
+    ptrs = [_ptr(r) for r in planes] + [None] * (3 - len(planes))
+    sc = [C.c_float(float(s)) for s in scales] + [C.c_float(0.0)] * (3 - len(planes))
+    st = _lib.lib().drc_head_gather_planar_fwd(ptrs[0], ptrs[1], ptrs[2], sc[0], sc[1], sc[2], len(planes), _ptr(res), _ptr(out), N, D, H, W, _stream_ptr(out.device))
+    _lib.check(st, "drc_head_gather_planar_fwd")
+
+
 def upsample_softargmin(cost, disp, maxdisp, mindisp):
     N, Dp, Hp, Wp = cost.shape
     _, H, W = disp.shape
@@ -1316,7 +1333,9 @@ def cost_volume16_blocked(left, right, out, lo4, hi4, in_blocked_pad=-1):
 HEAD_FUSED = {"enabled": True}       # eval, split-f16 regressor: classif[0] + the 32 -> 1 layer as one fused launch + a gather (convs16.hip HEAD form) instead of a blocked fp32 tensor + cout1_mfma.hip
 LASTCONV_S16 = {"enabled": True}     # eval, split-f16 2D schedule: lastconv[0] (320 -> 128) as three chained split-f16 launches over the concat's parts (runtime._ws2d_s16)
 S16 = {"enabled": True}       # eval: the stride-1 3x3x3 layers at full resolution on the f16 matrix cores in split arithmetic (convs16.hip)
+HEAD_SLOTS, HEAD_ROWS_LAYOUT, HEAD_PLANAR = 0, 1, 2   # drc_s16conv_params.head_rows: the layout of a fused head's partial sums (DRC_HEAD_* of include/disprcnn_hip.h)
 HEAD_ROWS = {"enabled": True}        # eval, fused heads on 28-column maps: the head launches sum the width taps (rows layout, 16 B per voxel) and ONE gather adds the three heads into cost3; False: the 12-float slots + a gather per head (A/B switch, read at every forward)
+HEAD_FLAT = {"enabled": True, "group": 4}    # eval, fused heads on 28-column maps: the head launches run on flat tiles (convs16.hip, DESIGN 3.18: planar partial sums, 36 B per voxel and head) and drc_head_gather_planar_fwd forms the width sums; the library keeps small launches on the rows layout; False: rows layout at every size; "force": True: flat whatever the launch's size (A/B switch, read when a workspace is planned)
 FLAT_TILES = {"enabled": True, "group": 4}   # the plain / residual 32 -> 32 layers on 28-column maps: MFMA tiles of 32 consecutive voxels of a group of `group` (4 or 1) units instead of one 28-voxel row (convs16.hip; the library keeps small launches on rows); False: row tiles; "force": True asks for flat tiles whatever the launch's size (A/B switch, read at every run())
 FLAT_TILES_HALF = {"enabled": True, "group": 8}   # the same switch for the hourglass' half-resolution 64 -> 64 layers on 14-column maps (conv2 of each hourglass): tiles of 32 consecutive voxels of a group of `group` (8, 4 or 1) units instead of 2 x 14; "force" as above (read at every run())
 CV_WIDE = {"enabled": True}   # eval, large batches: the cost-volume layer with two rows per work item (convs16w.hip); False: convs16.hip's one-row form (A/B switch, read at every run())
@@ -1590,16 +1609,43 @@ class ConvPlanS16:
             return 0x1000
         return (0x2000 if FLAT_TILES.get("force") else 0) | (0x4000 if int(FLAT_TILES["group"]) == 1 else 0)
 
-    def run(self, x16, w16, scale, shift, y16=None, y32=None, res=None, left=None, right=None, lo4=0, head=None, head_rows=False):
+    def _head_flat_bits(self):
+        """HEAD_FLAT as the library's `dil` bits (those of FLAT_TILES, _flat_bits)."""
+        if not HEAD_FLAT["enabled"]:
+            return 0x1000
+        return (0x2000 if HEAD_FLAT.get("force") else 0) | (0x4000 if int(HEAD_FLAT["group"]) == 1 else 0)
+
+    def head_flat(self):
+        """Units per group (4 or 1) where the library runs this plan as a fused head on flat tiles -- the planar layout, HEAD_PLANAR -- and 0
+        where it keeps the rows layout (drc_conv3d_k3_s16_flat, asked with stand-in pointers: host code, no launch; HEAD_FLAT's state now)."""
+        from ._lib import DrcS16ConvParams
+        if self.kind != "s1" or self.cv or not HEAD_FLAT["enabled"]:
+            return 0
+        probe = DrcS16ConvParams(1, 1, 1, 1, None, None, None, None, None, self.N, self.D, self.H, self.W, self.cin, self.cout, int(self.relu), 0,
+                                 1 | self._head_flat_bits(), 1, 1, None, HEAD_PLANAR)
+        return max(0, int(_lib.lib().drc_conv3d_k3_s16_flat(C.byref(probe))))
+
+    @property
+    def head_kname(self):
+        """The instantiation a fused-head launch of this plan runs where the caller follows head_flat() (PSMNet's runtime does)."""
+        return ("convs16_headflat_kernel<%d,false,0,28,false,false,true>" if self.head_flat() else "convs16_kernel<%d,false,1,28,false,false,true>") % (self.cin // 16)
+
+    def run(self, x16, w16, scale, shift, y16=None, y32=None, res=None, left=None, right=None, lo4=0, head=None, head_rows=False, head_layout=None):
         """head = (packed 32 -> 1 weights of s16.pack_head_weight_s16, S buffer fp32 of >= N*D*H*W*12 floats): the layer is classif[0] of a
         head, its output is not stored, the partial sums of the cout-1 layer behind it are (head_gather finishes it).  head_rows (W == 28): the
-        rows layout, S of >= N*D*H*W*4 floats, finished by head_gather_rows."""
+        rows layout, S of >= N*D*H*W*4 floats, finished by head_gather_rows.  head_layout = HEAD_PLANAR (W == 28): the flat-tile form, S of
+        >= N*D*9*H*W floats in planes, finished by head_gather_planar (HEAD_FLAT's group size; head_flat() says where the library prefers it)."""
         from ._lib import DrcS16ConvParams
+        if head_layout is None:
+            head_layout = HEAD_ROWS_LAYOUT if head_rows else HEAD_SLOTS
+        elif head_rows or head_layout not in (HEAD_SLOTS, HEAD_ROWS_LAYOUT, HEAD_PLANAR):
+            raise ValueError("ConvPlanS16.run: head_layout = HEAD_SLOTS | HEAD_ROWS_LAYOUT | HEAD_PLANAR (head_rows is the second one's older spelling)")
+        head_rows = head_layout != HEAD_SLOTS
         if head is not None:
             if self.kind != "s1" or self.cv or (self.cin, self.cout) != (32, 32) or self.W % 28 or self.D < 6 or self.D % 3 or y16 is not None or y32 is not None or res is not None:
                 raise ValueError("ConvPlanS16.run: the fused head is the 32 -> 32 full-resolution layer without another output")
-            if head[1].dtype != torch.float32 or head[1].numel() < self.N * self.D * self.H * self.W * (4 if head_rows else 12) or head[0].dtype != torch.float16 or head[0].numel() != 2048:
-                raise ValueError("ConvPlanS16.run: head = (halfs [2][2][64][8], fp32 buffer of N*D*H*W*12; rows layout: *4)")
+            if head[1].dtype != torch.float32 or head[1].numel() < self.N * self.D * self.H * self.W * {HEAD_SLOTS: 12, HEAD_ROWS_LAYOUT: 4, HEAD_PLANAR: 9}[head_layout] or head[0].dtype != torch.float16 or head[0].numel() != 2048:
+                raise ValueError("ConvPlanS16.run: head = (halfs [2][2][64][8], fp32 buffer of N*D*H*W*12; rows layout: *4; planar: *9)")
         elif head_rows:
             raise ValueError("ConvPlanS16.run: head_rows is a layout of the fused head")
         if x16 is not None and (x16.N < self.N or (x16.C, x16.D, x16.H, x16.W, x16.pd) != (self.cin, self.D, self.H, self.W, self.pd)):
@@ -1623,8 +1669,8 @@ class ConvPlanS16:
                              _ptr(res.storage) if res is not None else None, _ptr(y16.storage) if y16 is not None else None,
                              _ptr(y32.storage) if y32 is not None else None, _ptr(left.storage) if self.cv else None,
                              _ptr(right.storage) if self.cv else None, self.N, self.D, self.H, self.W, self.cin, self.cout, int(self.relu), int(lo4),
-                             0x800 if (self.cv and self.kind == "s1" and not CV_WIDE["enabled"]) else int(self.dil) | self._flat_bits(),   # (the library's switch bits of the 3D layers' unused `dil` field: keep the one-row kernel; row / flat tiles)
-                             _ptr(head[1]) if head is not None else None, _ptr(head[0]) if head is not None else None, _ovf_ptr(), int(bool(head_rows)))
+                             0x800 if (self.cv and self.kind == "s1" and not CV_WIDE["enabled"]) else int(self.dil) | (self._head_flat_bits() & 0x4000 if head_layout == HEAD_PLANAR else self._flat_bits()),   # (the library's switch bits of the 3D layers' unused `dil` field: keep the one-row kernel; row / flat tiles; the planar head IS the flat form: its group size only)
+                             _ptr(head[1]) if head is not None else None, _ptr(head[0]) if head is not None else None, _ovf_ptr(), int(head_layout))
         dev = self.device
         e0 = None if TIMING is None else _timing_start(dev)
         fn = {"s1": "drc_conv3d_k3_s16_fwd", "s2": "drc_conv3d_k3s2_s16_fwd", "up": "drc_deconv3d_k3s2_s16_fwd", "2d": "drc_conv2d_k3_s16_fwd"}[self.kind]

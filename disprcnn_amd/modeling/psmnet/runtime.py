@@ -274,11 +274,13 @@ class _SplitF16(_Blocked32):
     @staticmethod
     def head_tensors(ws, N, full):
         # the heads: classif[0] + the 32 -> 1 layer fused (convs16.hip HEAD form: partial sums S, 48 B per voxel, one buffer for the three
-        # heads) where the map is a multiple of 28 columns; else classif[0] writes a blocked fp32 tensor that cout1_mfma.hip reads
+        # heads) where the map is a multiple of 28 columns; else classif[0] writes a blocked fp32 tensor that cout1_mfma.hip reads.  On
+        # 28-column maps the buffer holds three heads in the planar layout of the flat-tile form (3 x 36 B per voxel; the rows layout's
+        # 3 x 16 B fit in front): one size per geometry, whatever the unit count and engine.HEAD_FLAT say at a later forward
         t, pool = ws["t"], ws["pool"]
         ws["fused_heads"] = E.HEAD_FUSED["enabled"] and full[2] % 28 == 0 and full[0] >= 6 and full[0] % 3 == 0
         if ws["fused_heads"]:
-            t["hs"] = pool.dense("hs", N, *full, 12)
+            t["hs"] = pool.dense("hs", N, *full, 27 if full[2] == 28 else 12)
         else:
             for h in REGRESSOR_HEADS:
                 t[h.cls_t] = pool.blocked(h.cls_t, N, 32, *full, 1, 1, 1)    # fp32: the cout-1 head reads it
@@ -312,10 +314,13 @@ class _SplitF16(_Blocked32):
         if h16 is not None and E.HEAD_ROWS["enabled"] and t["costk3"].shape[-1] == 28:
             # one x tile per row: the head launches sum the width taps themselves (rows layout, 16 B per voxel: the S buffer holds all three
             # heads) and ONE gather adds the three heads into cost3 -- cost1 / cost2 are the training path's and are not produced here
+            # From the library's lower bound on (ConvPlanS16.head_flat: 2048 flat columns) the heads run on flat 32-voxel tiles, which store the
+            # nine partial sums per source voxel in planes, and the gather forms the width sums as well -- same sums, same order, same bits
             rows = t["hs"].view(3, -1)
+            planar = bool(ws["heads"][0][0][0].head_flat())
             for e, h in ws["heads"]:
-                run(*e, head=(h16[h.k][0], rows[h.k - 1]), head_rows=True)
-            E.head_gather_rows([rows[0], rows[1], rows[2]], [h16[k][1] for k in (1, 2, 3)], None, t["costk3"])
+                run(*e, head=(h16[h.k][0], rows[h.k - 1]), head_layout=E.HEAD_PLANAR if planar else E.HEAD_ROWS_LAYOUT)
+            (E.head_gather_planar if planar else E.head_gather_rows)([rows[0], rows[1], rows[2]], [h16[k][1] for k in (1, 2, 3)], None, t["costk3"])
             return None, None, t["costk3"]
         for e, h in ws["heads"]:
             if h16 is not None:
@@ -796,7 +801,7 @@ class PSMNetRuntime:
         m = self.model
         return (m.maxdisp, m.mindisp, getattr(m, "regressor_math", "auto"), getattr(m, "regressor_storage", "f32"),
                 getattr(m, "feature_storage", "f32"), getattr(m, "feature_math", "auto"),
-                E.S16["enabled"], E.HEAD_FUSED["enabled"], E.LASTCONV_S16["enabled"], E.TRUNK_S16["enabled"], E.CV_WIDE["enabled"], E.HEAD_ROWS["enabled"], E.s16_allowed(),
+                E.S16["enabled"], E.HEAD_FUSED["enabled"], E.LASTCONV_S16["enabled"], E.TRUNK_S16["enabled"], E.CV_WIDE["enabled"], E.HEAD_ROWS["enabled"], tuple(sorted(E.HEAD_FLAT.items())), E.s16_allowed(),
                 id(E.guard_in_scope()))
 
     def forward_features(self, fl, fr, out_hw, training=False):

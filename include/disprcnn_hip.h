@@ -388,8 +388,16 @@ typedef struct drc_s16conv_params {
     int32_t head_rows;   /* with head, W == 28 (else -4): the ROWS layout of the partial sums, float [N][D][H][W][4] = (T0, T1a, T1b, T2) per source
                             row and OUTPUT column -- the width taps summed in the kernel: T0 = (S0[x-1] + S1[x]) + S2[x+1], T1a = S3[x-1] + S4[x],
                             T1b = S5[x+1], T2 = (S6[x-1] + S7[x]) + S8[x+1] (a column outside the map adds zero).  drc_head_gather_rows_fwd
-                            finishes the layer.  0: the 12-float layout above. */
+                            finishes the layer.  0: the 12-float layout above.
+                            The field names the layout of `head`, one of DRC_HEAD_SLOTS (0), DRC_HEAD_ROWS (1) and DRC_HEAD_PLANAR (2, round 14; W == 28,
+                            else -4): float [N][D][9][H W], plane j = kh*3 + kw of the nine depth-summed sums of the SOURCE voxel y W + x, nothing
+                            summed over the width.  It is what the flat-tile head form writes, so asking for it asks for that form whatever the
+                            launch's size (drc_conv3d_k3_s16_flat says whether the library would choose it); drc_head_gather_planar_fwd finishes
+                            the layer with the sums, in the order, of the rows layout. */
 } drc_s16conv_params;
+#define DRC_HEAD_SLOTS 0
+#define DRC_HEAD_ROWS 1
+#define DRC_HEAD_PLANAR 2
 int drc_conv3d_k3_s16_supported(int cin, int cout, int D, int H, int W);
 int drc_conv3d_k3_s16_fwd(const drc_s16conv_params* p, void* stream);
 /* The cost-volume form (left / right set) is computed from per-row 2D tap maps (round 8, s16_cvrows.h): the vertical (kh, channel)
@@ -409,7 +417,9 @@ int drc_conv3d_k3_s16_wide(const drc_s16conv_params* p);
  * four waves split K, so a column is ONE tile of 32 consecutive voxels of a group of eight units (or four, or one): 49 instead of 56 columns per
  * eight 14 x 14 planes, bit-identical to the row tiles.  Chosen from 1176 columns of 32 voxels on (192 Config-A ROIs); the library walks the
  * columns of the launch on the host and refuses the form (0, or -4 when forced) if a column's slab would need more than 8 stacked rows or reach
- * more than 3 units behind its first one.  Return values 1 | 4 | 8 = the group size. */
+ * more than 3 units behind its first one.  Return values 1 | 4 | 8 = the group size.
+ * The fused head on flat tiles (round 14; p->head with head_rows == DRC_HEAD_PLANAR, cin = cout = 32, W == 28, D >= 6, D % 3 == 0): the 32 -> 32
+ * form's columns, groups (four units, or one) and lower bound of 2048 columns; with any other head layout the answer stays 0 (-4 when forced). */
 int drc_conv3d_k3_s16_flat(const drc_s16conv_params* p);
 int drc_conv3d_k3_s16_wide_fwd(const drc_s16conv_params* p, void* stream);
 /* The second half of a fused head (p->head above): cost[n][z][y][x] = (res ? res[..] : 0) + scale * sum_{kh,kw} S[n][z][y+kh-1][x+kw-1][kh*3+kw]
@@ -422,6 +432,12 @@ int drc_head_gather_fwd(const float* S, const float* res, float* cost, int N, in
  * aligned; rows / scales of k >= nheads are ignored. */
 int drc_head_gather_rows_fwd(const float* rows0, const float* rows1, const float* rows2, float scale0, float scale1, float scale2, int nheads,
                              const float* res, float* cost, int N, int D, int H, int W, void* stream);
+/* The same for 1 to 3 fused heads in the planar layout (DRC_HEAD_PLANAR above; s_k: float [N][D][9][H W]): per head and source row r,
+ *   T0 = (S0[r][x-1] + S1[r][x]) + S2[r][x+1], T1a = S3[r][x-1] + S4[r][x], T1b = S5[r][x+1], T2 = (S6[r][x-1] + S7[r][x]) + S8[r][x+1]
+ * (a column outside [0, W) enters as +0.0f, the add is performed), then the expression of drc_head_gather_rows_fwd: the same additions in the
+ * same order as the rows layout's conv kernel + gather, bit-identical to them. */
+int drc_head_gather_planar_fwd(const float* s0, const float* s1, const float* s2, float scale0, float scale1, float scale2, int nheads,
+                               const float* res, float* cost, int N, int D, int H, int W, void* stream);
 /* The hourglass' other 3x3x3 layers in the same arithmetic and layout (x, y16, res: RS16; no blocked fp32 output, no cost-volume form):
  *   drc_conv3d_k3s2_s16_fwd   -- Conv3d k3 s2 p1 + BN + ReLU (convs16d.hip; reference hourglass conv1 / conv3, stackhourglass.py:9-12,17-19).
  *                                D, H, W = the INPUT dims (even); y16 has (D/2, H/2, W/2); no residual.
