@@ -49,34 +49,60 @@ WGRAD_TILE = {"lds_cap": 12 * 1024, "lds_max": 38 * 1024}
 WGRAD_PARTIALS = {"enabled": True}     # partial sums + fixed-order reduce instead of the atomicAdd flush (tests flip it)
 
 
-def wgrad(a, b, cls, in_mul, R=None, WT=None):
-    """gw[cbA*16][cbB*16][T] for one tap class (see include/disprcnn_hip.h: drc_tapconv_wgrad)."""
-    dev = a.device
-    nd, nh, nw = cls["n"]
-    T = nd * nh * nw
-    gw = torch.empty(a.cb * 16, b.cb * 16, T, dtype=torch.float32, device=dev)
-    p = DrcWgradParams()
-    p.overwrite = 1                       # no zero-fill launch: the kernels store (or clear gw themselves on the atomicAdd path)
-    span_h, span_w = (nh - 1) * cls["step"][1], (nw - 1) * cls["step"][2]
-    # tile: R rows x WT cols of b with (rows_in*seg + R*WT)*64 B <= 38 KiB per wave
+def wgrad_tile_need(R, WT, in_mul, span_h, span_w):
+    """LDS bytes of one wave's (a, b) tile pair: ((rows_in * seg_vox) + R * WT) * 64, as drc_tapconv_wgrad checks it."""
+    return ((in_mul * (R - 1) + span_h + 1) * (in_mul * (WT - 1) + span_w + 1) + R * WT) * 64
+
+
+def wgrad_tile_search(H, W, in_mul, span_h, span_w):
+    """(R, WT, need): the tile of R rows x WT columns of b the generic kernel walks an H x W map with, and its LDS bytes per wave.  A pure
+    function of its arguments and WGRAD_TILE; None if no tile fits."""
     best = None
     # (strided taps -- in_mul = 2: the stride-2 convolutions and the transposed ones -- keep the large tiles: their a tile is 4x the b tile
     # and small caps leave only ragged tiles; Config-A step 17.19 vs 17.33 ms)
     for cap in ((WGRAD_TILE["lds_cap"], WGRAD_TILE["lds_max"]) if in_mul == 1 else (WGRAD_TILE["lds_max"],)):
-        for wt in sorted({-(-b.W // k) for k in range(1, b.W + 1) if -(-b.W // k) <= 112}):
-            for r in range(1, min(b.H, 112 // wt) + 1):
-                need = ((in_mul * (r - 1) + span_h + 1) * (in_mul * (wt - 1) + span_w + 1) + r * wt) * 64
+        for wt in sorted({-(-W // k) for k in range(1, W + 1) if -(-W // k) <= 112}):
+            for r in range(1, min(H, 112 // wt) + 1):
+                need = wgrad_tile_need(r, wt, in_mul, span_h, span_w)
                 if need > cap:
                     continue
-                eff = (b.H * b.W) / ((-(-b.H // r)) * (-(-b.W // wt)) * (-(-(r * wt) // 4)) * 4)
+                eff = (H * W) / ((-(-H // r)) * (-(-W // wt)) * (-(-(r * wt) // 4)) * 4)
                 key = (round(eff, 3), r * wt, wt)
                 if best is None or key > best[0]:
                     best = (key, r, wt, need)
         if best is not None:
             break
+    return None if best is None else best[1:]
+
+
+def wgrad(a, b, cls, in_mul, R=None, WT=None, overwrite=1, gw=None, scratch_floats=None):
+    """gw[cbA*16][cbB*16][T] for one tap class (see include/disprcnn_hip.h: drc_tapconv_wgrad).
+    R, WT: the generic kernel's tile instead of the searched one (both or neither).  overwrite=0 with a given `gw` adds the gradient onto
+    it.  scratch_floats: how much of the partial-sum workspace the launch may use (default: all of it)."""
+    dev = a.device
+    nd, nh, nw = cls["n"]
+    T = nd * nh * nw
+    if gw is None:
+        if not overwrite:
+            raise ValueError("wgrad: overwrite=0 adds onto a given gw")
+        gw = torch.empty(a.cb * 16, b.cb * 16, T, dtype=torch.float32, device=dev)
+    elif tuple(gw.shape) != (a.cb * 16, b.cb * 16, T) or gw.dtype != torch.float32 or not gw.is_contiguous():
+        raise ValueError("wgrad: gw must be a contiguous fp32 [cbA*16][cbB*16][T] tensor")
+    if b.N == 0:                          # the C entry returns before any store: an empty batch has a zero gradient
+        return gw.zero_() if overwrite else gw
+    p = DrcWgradParams()
+    p.overwrite = int(bool(overwrite))    # 1: no zero-fill launch, the kernels store (or clear gw themselves on the atomicAdd path)
+    span_h, span_w = (nh - 1) * cls["step"][1], (nw - 1) * cls["step"][2]
+    # tile: R rows x WT cols of b with (rows_in*seg + R*WT)*64 B <= 38 KiB per wave
+    if (R is None) != (WT is None):
+        raise ValueError("wgrad: give both R and WT, or neither")
+    if R is not None:
+        best = (int(R), int(WT), wgrad_tile_need(int(R), int(WT), in_mul, span_h, span_w))
+    else:
+        best = wgrad_tile_search(b.H, b.W, in_mul, span_h, span_w)
     if best is None:
         raise ValueError("wgrad: no tile fits LDS")
-    _, p.R, p.WT, need = best
+    p.R, p.WT, need = best
     p.lds_bytes_per_wave = (need + 1023) // 1024 * 1024
     p.a, p.b, p.gw = E._base_ptr(a), E._base_ptr(b), gw.data_ptr()
     p.a_n_stride, p.a_cb_stride, p.a_d_stride, p.a_h_stride = a.n_stride, a.cb_stride, a.d_stride, a.h_stride
@@ -89,7 +115,7 @@ def wgrad(a, b, cls, in_mul, R=None, WT=None):
     p.sd, p.sh, p.sw = cls["step"]
     if WGRAD_PARTIALS["enabled"]:
         scratch = E.wgrad_scratch(dev)
-        p.scratch, p.scratch_floats = scratch.data_ptr(), scratch.numel()
+        p.scratch, p.scratch_floats = scratch.data_ptr(), scratch.numel() if scratch_floats is None else min(int(scratch_floats), scratch.numel())
     st = _lib.lib().drc_tapconv_wgrad(C.byref(p), E._stream_ptr(dev))
     _lib.check(st, "drc_tapconv_wgrad")
     return gw

@@ -1,6 +1,11 @@
 """GPU tests of the train-mode forward (per-GPU batch-statistics BatchNorm, three heads) against the CPU oracle and the
 reference's recorded train-mode outputs (tests/golden: Bt_*).  Tolerances: BN statistics 1e-5 relative; disparities
-mean <= 2e-3 px (batch-stat BN through ~60 layers on an untrained, saturating net)."""
+mean <= 2e-3 px (batch-stat BN through ~60 layers on an untrained, saturating net).
+
+The backward's kernels are held to fp64 at the edges of their grids elsewhere: the BatchNorm and loss reductions in
+test_hip_train_reductions.py, the classifier / cost-volume / SPP adjoints in test_hip_train_adjoints.py, the weight-gradient kernels
+(drc_tapconv_wgrad: every tile, segment and flush form) in test_hip_wgrad_edges.py.  The wgrad and per-site tests here are max-norm
+checks at friendly sizes."""
 import copy
 
 import pytest
