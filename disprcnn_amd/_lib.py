@@ -110,6 +110,9 @@ _SIGS = {
     "drc_act_bwd_rows": (_I, [_P, _P, _P, C.c_float, _I, _I, _I, _I, _P, _P, _P, C.c_int64, _P]),
     "drc_act_bwd_blocked_scratch_doubles": (C.c_int64, [_I, _I, _I]),
     "drc_act_bwd_blocked": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, C.c_int64, _P]),
+    "drc_bilinear_resize_blocked_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "drc_channel_sums_blocked_scratch_doubles": (C.c_int64, [_I, _I, _I]),
+    "drc_channel_sums_blocked": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, C.c_int64, _P]),
     "drc_roi_align_fpn_bwd": (_I, [C.POINTER(DrcFpnPyramid), _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "drc_srpn_active_pixels": (_I, [C.POINTER(DrcSrpnLevels), _P, _P, _P, _P, _P, _P]),
     "drc_srpn_gather_rows": (_I, [C.POINTER(DrcSrpnLevels), _P, _P, _P, _P, _P, _P, _P]),

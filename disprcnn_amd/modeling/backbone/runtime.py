@@ -65,6 +65,139 @@ def _half(n):       # conv k1/k3 stride 2 (pad k//2) and max_pool2d(1,2,0): floo
     return (n - 1) // 2 + 1
 
 
+def _plan_fpn(t, p, stage_out, och, B2, bridge):
+    """The FPN's tensors and plans (top-down; fpn.py:44-77) behind the stage outputs stage_out = [(tensor name, channels, (h, w))] x 4,
+    added to t / p.  -> (schedule, names of the five output maps, (h, w) of the top level)."""
+    fsched, outs = [], [None] * 5
+    top, tch, thw = stage_out[3]
+    t["in4"] = B2(och, thw[0], thw[1], 1)
+    p["inner4"] = E.plan_conv2d(t[top], t["in4"], 1, 1, 0, 1, och, False)
+    fsched.append(("conv", "inner4", top, "in4", None))
+    outs[3] = "in4"                                                 # top level: no 3x3 block (fork quirk)
+    last, lhw = "in4", thw
+    for i in (3, 2, 1):
+        feat, fch, fhw = stage_out[i - 1]
+        t[f"td{i}"] = B2(och, fhw[0], fhw[1], 0)
+        t[f"sum{i}"] = B2(och, fhw[0], fhw[1], 1)
+        t[f"out{i}"] = B2(och, fhw[0], fhw[1], 1)                 # halo 1: FPN top-down reads out3/out2, the RPN head all levels
+        p[f"inner{i}"] = E.plan_conv2d(t[feat], t[f"sum{i}"], 1, 1, 0, 1, och, False)
+        p[f"layer{i}"] = E.plan_conv2d(t[f"sum{i}"], t[f"out{i}"], 3, 1, 1, 1, och, False)
+        fsched.append(("resize", last, f"td{i}", lhw, fhw))
+        fsched.append(("conv", f"inner{i}", feat, f"sum{i}", f"td{i}"))      # inner_lateral + inner_top_down
+        fsched.append(("conv", f"layer{i}", f"sum{i}", f"out{i}", None))
+        bridge(f"layer{i}", och, och, fhw[0], fhw[1], False)
+        outs[i - 1] = f"out{i}"
+        last, lhw = f"out{i}", fhw                                  # reference: last_inner = layer_block(lateral + top_down)
+    t["p6"] = B2(och, _half(thw[0]), _half(thw[1]), 1)
+    outs[4] = "p6"
+    return fsched, outs, thw
+
+
+def _run_fpn(ws, N, conv, device):
+    """The FPN schedule of a workspace: conv(plan, x, y, res) runs a convolution site, the resizes and the P6 subsample run here."""
+    t = ws["t"]
+    lib, sp = _lib.lib(), E._stream_ptr(device)
+    for item in ws["fsched"]:
+        if item[0] == "conv":
+            conv(item[1], item[2], item[3], item[4])
+        else:
+            _, src, dst, (ih, iw), (oh, ow) = item
+            cb = t[src].cb
+            _lib.check(lib.drc_bilinear_resize_blocked(E._ptr(t[src].storage), E._ptr(t[dst].storage), N, cb, ih, iw, t[src].ph, oh, ow,
+                                                       t[dst].ph, cb, 0, 0, sp), "drc_bilinear_resize_blocked")
+    th, tw = ws["thw"]
+    _lib.check(lib.drc_maxpool2d_blocked(E._ptr(t["in4"].storage), E._ptr(t["p6"].storage), N, t["in4"].cb, th, tw, t["in4"].ph, 1, 2,
+                                         t["p6"].H, t["p6"].W, t["p6"].ph, sp), "drc_maxpool2d_blocked")
+
+
+def _fp32_conv(ws, Wt):
+    """conv(plan, x, y, res) on the fp32 plans only (the training forms: no split-f16 bridge)."""
+    t, p = ws["t"], ws["p"]
+
+    def conv(plan, x_, y_, res=None):
+        c = Wt[plan]
+        p[plan].run(t[x_], c.w, c.scale, c.shift, t[y_], t[res] if res else None, w16=_w16_for(c, p[plan]))
+    return conv
+
+
+def _dense_outputs(rt, ws):
+    """The five dense maps of the workspace's pyramid, stamped with the generation of the blocked tensors they were read from."""
+    t = ws["t"]
+    rt._levels = [t[o] for o in ws["outs"]]
+    rt._gen = getattr(rt, "_gen", 0) + 1
+    outs = tuple(t[o].to_dense()[:, :, 0] for o in ws["outs"])
+    for o in outs:
+        o._drc_pyramid_gen = (id(rt), rt._gen)
+    return outs
+
+
+class FPNRuntime:
+    """A bare FPN module on the HIP engine, behind given C2..C5 maps (dense [N, C_i, h_i, w_i]): the schedule BackboneRuntime runs behind
+    its ResNet body, on the fp32 plans (small pyramids never reach the split-f16 bridge's thresholds).  `forward` is the eval form;
+    fpn_train.fpn_train the training form on the same workspace."""
+
+    def __init__(self, fpn, device):
+        if fpn.levels != 4:
+            raise NotImplementedError("FPNRuntime: four pyramid levels (C2..C5)")
+        self.fpn, self.device = fpn, device
+        self._w, self._ver, self._ws, self._levels, self._gen = None, None, {}, None, 0
+
+    def _compile(self):
+        ps = list(self.fpn.parameters())
+        v = ([p_._version for p_ in ps], [p_.data_ptr() for p_ in ps])
+        if self._w is None or v != self._ver:
+            W = {}
+            for i in range(1, 5):
+                W[f"inner{i}"] = _Site(getattr(self.fpn, f"fpn_inner{i}"), None, self.device)
+                W[f"layer{i}"] = _Site(getattr(self.fpn, f"fpn_layer{i}"), None, self.device)
+            self._w, self._ver = W, v
+        return self._w
+
+    def _workspace(self, N, shapes):
+        key = (N,) + tuple(shapes)
+        if key in self._ws:
+            return self._ws[key]
+        B2 = lambda c, h, w, pad: E.Blocked(N, c, 1, h, w, 0, pad, pad, self.device)
+        t, p, stage_out = {}, {}, []
+        for i, (c, h, w) in enumerate(shapes, 1):
+            t[f"c{i}"] = B2(c, h, w, 0)
+            stage_out.append((f"c{i}", c, (h, w)))
+        fsched, outs, thw = _plan_fpn(t, p, stage_out, self.fpn.fpn_inner4.out_channels, B2, lambda *a: None)
+        ws = self._ws[key] = dict(t=t, p=p, fsched=fsched, outs=outs, thw=thw, s16={}, stage_out=stage_out)
+        while len(self._ws) > 8:
+            self._ws.pop(next(iter(self._ws)))
+        return ws
+
+    def load(self, features):
+        """The workspace of these C maps, with the maps written into its blocked inputs."""
+        if len(features) != 4:
+            raise ValueError("FPNRuntime: four feature maps (C2..C5) expected")
+        N = features[0].shape[0]
+        shapes = []
+        for i, f in enumerate(features, 1):
+            E.require_gpu(f, "FPN input")
+            if f.dim() != 4 or f.shape[0] != N or f.shape[1] != getattr(self.fpn, f"fpn_inner{i}").in_channels:
+                raise ValueError(f"FPNRuntime: C{i + 1} of shape {tuple(f.shape)} does not fit fpn_inner{i}")
+            shapes.append(tuple(int(v) for v in f.shape[1:]))
+        for a, b in zip(shapes[:-1], shapes[1:]):
+            if b[1] > a[1] or b[2] > a[2]:
+                raise ValueError("FPNRuntime: the maps must not grow towards the top of the pyramid")
+        ws = self._workspace(N, shapes)
+        for i, f in enumerate(features, 1):
+            ws["t"][f"c{i}"].from_dense(f.detach())
+        return ws, N
+
+    def forward(self, features):
+        with torch.no_grad():
+            ws, N = self.load(features)
+            _run_fpn(ws, N, _fp32_conv(ws, self._compile()), self.device)
+            return _dense_outputs(self, ws)
+
+    def blocked_levels(self, dense_outputs=None):
+        """As BackboneRuntime.blocked_levels."""
+        return BackboneRuntime.blocked_levels(self, dense_outputs)
+
+
 class BackboneRuntime:
     def __init__(self, model, device):
         self.model, self.device = model, device
@@ -91,17 +224,26 @@ class BackboneRuntime:
         if self._w is not None and v == self._ver:
             return self._w
         body, fpn, dev = self.model.body, self.model.fpn, self.device
-        W = {"stem": _Site(body.stem.conv1, body.stem.bn1, dev, _stem_s2d_weight)}
+        old, W = getattr(self, "_site_keys", {}), {}
+        keys = {}
+
+        def site(name, conv, bn, weight_fn=None):
+            # a site is rebuilt only when one of ITS tensors changed: a training step that updates the FPN leaves the body's packings alone
+            ts = [conv.weight, conv.bias] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps] if bn is not None else [])
+            keys[name] = [(x._version, x.data_ptr()) if isinstance(x, torch.Tensor) else x for x in ts]
+            W[name] = self._w[name] if self._w is not None and old.get(name) == keys[name] else _Site(conv, bn, dev, weight_fn)
+
+        site("stem", body.stem.conv1, body.stem.bn1, _stem_s2d_weight)
         for li in range(1, 5):
             for b, u in enumerate(getattr(body, f"layer{li}")):
                 p = f"l{li}.{b}"
-                W[p + ".c1"], W[p + ".c2"], W[p + ".c3"] = _Site(u.conv1, u.bn1, dev), _Site(u.conv2, u.bn2, dev), _Site(u.conv3, u.bn3, dev)
+                site(p + ".c1", u.conv1, u.bn1), site(p + ".c2", u.conv2, u.bn2), site(p + ".c3", u.conv3, u.bn3)
                 if u.downsample is not None:
-                    W[p + ".ds"] = _Site(u.downsample[0], u.downsample[1], dev)
+                    site(p + ".ds", u.downsample[0], u.downsample[1])
         for i in range(1, 5):
-            W[f"inner{i}"] = _Site(getattr(fpn, f"fpn_inner{i}"), None, dev)
-            W[f"layer{i}"] = _Site(getattr(fpn, f"fpn_layer{i}"), None, dev)
-        self._w, self._ver = W, v
+            site(f"inner{i}", getattr(fpn, f"fpn_inner{i}"), None)
+            site(f"layer{i}", getattr(fpn, f"fpn_layer{i}"), None)
+        self._w, self._ver, self._site_keys = W, v, keys
         return W
 
     def _workspace(self, N, H, W_):
@@ -150,30 +292,8 @@ class BackboneRuntime:
                 bridge(q + ".c2", mid, mid, ohw[0], ohw[1], True)
                 cur, ch, hw = q + ".o", cout, ohw
             stage_out.append((cur, ch, hw))
-        # FPN (top-down)
-        fsched, outs = [], [None] * 5
-        top, tch, thw = stage_out[3]
-        t["in4"] = B2(256, thw[0], thw[1], 1)
-        p["inner4"] = E.plan_conv2d(t[top], t["in4"], 1, 1, 0, 1, 256, False)
-        fsched.append(("conv", "inner4", top, "in4", None))
-        outs[3] = "in4"                                                 # top level: no 3x3 block (fork quirk)
-        last, lhw = "in4", thw
-        for i in (3, 2, 1):
-            feat, fch, fhw = stage_out[i - 1]
-            t[f"td{i}"] = B2(256, fhw[0], fhw[1], 0)
-            t[f"sum{i}"] = B2(256, fhw[0], fhw[1], 1)
-            t[f"out{i}"] = B2(256, fhw[0], fhw[1], 1)                 # halo 1: FPN top-down reads out3/out2, the RPN head all levels
-            p[f"inner{i}"] = E.plan_conv2d(t[feat], t[f"sum{i}"], 1, 1, 0, 1, 256, False)
-            p[f"layer{i}"] = E.plan_conv2d(t[f"sum{i}"], t[f"out{i}"], 3, 1, 1, 1, 256, False)
-            fsched.append(("resize", last, f"td{i}", lhw, fhw))
-            fsched.append(("conv", f"inner{i}", feat, f"sum{i}", f"td{i}"))      # inner_lateral + inner_top_down
-            fsched.append(("conv", f"layer{i}", f"sum{i}", f"out{i}", None))
-            bridge(f"layer{i}", 256, 256, fhw[0], fhw[1], False)
-            outs[i - 1] = f"out{i}"
-            last, lhw = f"out{i}", fhw                                  # reference: last_inner = layer_block(lateral + top_down)
-        t["p6"] = B2(256, _half(thw[0]), _half(thw[1]), 1)
-        outs[4] = "p6"
-        ws = dict(t=t, p=p, sched=sched, fsched=fsched, outs=outs, pool=(h1, w1, ph, pw), thw=thw, s16=s16b,
+        fsched, outs, thw = _plan_fpn(t, p, stage_out, self.model.fpn.fpn_inner4.out_channels, B2, bridge)
+        ws = dict(t=t, p=p, sched=sched, fsched=fsched, outs=outs, pool=(h1, w1, ph, pw), thw=thw, s16=s16b, stage_out=stage_out,
                   flops=sum(pl.flops for pl in p.values()))
         self._ws[key] = ws
         return ws
@@ -190,7 +310,21 @@ class BackboneRuntime:
         return E.guarded(self._guard, lambda: self._forward_once(x), what="ResNet-FPN trunk (split-f16 3x3 layers)",
                          enabled=bool(getattr(self.model, "overflow_check", True)))
 
-    def _forward_once(self, x):
+    def forward_fpn_train(self, x):
+        """The training form behind a frozen body: the stem and the four stages run their eval schedule under no_grad inside the range
+        guard; the FPN then runs through fpn_train's autograd Function on the fp32 plans, reading the stage outputs from the workspace."""
+        from . import fpn_train
+        E.require_gpu(x, "backbone input")
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"expected [N,3,H,W], got {tuple(x.shape)}")
+        if getattr(self, "_guard", None) is None:
+            self._guard = E.OverflowGuard(self.device)
+        with torch.no_grad():
+            ws = E.guarded(self._guard, lambda: self._forward_once(x, body_only=True), what="ResNet body (split-f16 3x3 layers)",
+                           enabled=bool(getattr(self.model, "overflow_check", True)))
+        return fpn_train.run(self, self.model.fpn, ws, x.shape[0], [None] * 4)      # (a module: the package does not re-export its function)
+
+    def _forward_once(self, x, body_only=False):
         N, _, H, W_ = x.shape
         Wt = self._compile()
         ws = self._workspace(N, H, W_)
@@ -215,22 +349,10 @@ class BackboneRuntime:
                    "drc_maxpool2d_blocked")
         for plan, x_, y_, res in ws["sched"]:
             conv(plan, x_, y_, res)
-        for item in ws["fsched"]:
-            if item[0] == "conv":
-                conv(item[1], item[2], item[3], item[4])
-            else:
-                _, src, dst, (ih, iw), (oh, ow) = item
-                _lib.check(lib.drc_bilinear_resize_blocked(E._ptr(t[src].storage), E._ptr(t[dst].storage), N, 16, ih, iw, t[src].ph, oh, ow,
-                                                           t[dst].ph, 16, 0, 0, sp), "drc_bilinear_resize_blocked")
-        th, tw = ws["thw"]
-        _lib.check(lib.drc_maxpool2d_blocked(E._ptr(t["in4"].storage), E._ptr(t["p6"].storage), N, 16, th, tw, t["in4"].ph, 1, 2,
-                                             t["p6"].H, t["p6"].W, t["p6"].ph, sp), "drc_maxpool2d_blocked")
-        self._levels = [t[o] for o in ws["outs"]]
-        self._gen = getattr(self, "_gen", 0) + 1
-        outs = tuple(t[o].to_dense()[:, :, 0] for o in ws["outs"])
-        for o in outs:                                   # the dense maps carry the generation of the blocked workspace they were read from
-            o._drc_pyramid_gen = (id(self), self._gen)
-        return outs
+        if body_only:
+            return ws
+        _run_fpn(ws, N, conv, self.device)
+        return _dense_outputs(self, ws)          # the dense maps carry the generation of the blocked workspace they were read from
 
     def blocked_levels(self, dense_outputs=None):
         """The pyramid in the engine's blocked layout (halo 1), for consumers that run on the engine themselves (the Stereo-RPN head).

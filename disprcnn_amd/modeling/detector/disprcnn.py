@@ -11,8 +11,10 @@ and DET3D_ON are separate models downstream and raise.
 Training runs with the trunk frozen (the reference's SOLVER.FIX_BACKBONE): every backbone parameter has requires_grad False, the backbone
 runs in its eval form under no_grad (its range guard around the backbone only), and the Stereo RPN and the ROI heads train on its
 features: forward(lrimages, lrtargets) returns the merged loss dict (loss_classifier, loss_box_reg, loss_mask, loss_objectness,
-loss_rpn_box_reg).  A sub-module in eval mode contributes no losses (the reference's FIX_RPN / FIX_BOX_HEAD).  What is still missing
-for training the whole 2D stage: the trunk's backward only."""
+loss_rpn_box_reg).  A sub-module in eval mode contributes no losses (the reference's FIX_RPN / FIX_BOX_HEAD).  With only backbone.fpn.*
+trainable and the body in eval (backbone.freeze_body()) the backbone runs in its training form instead -- frozen body under no_grad, the
+FPN as an autograd Function (backbone/fpn_train.py) -- and the five losses reach the FPN's parameters.  What is still missing for
+training the whole 2D stage: the ResNet body's backward (batch-statistics BatchNorm, bottleneck backward) only."""
 from types import SimpleNamespace
 
 import torch
@@ -61,13 +63,15 @@ class DispRCNN(nn.Module):
         """draws (training): optionally {'rpn_sample', 'sample', 'dropout'} -- the randomness of the RPN's sampler and of the box head
         (StereoRPN.forward, ROIBoxHead), so that a step can be repeated."""
         if self.training:
-            if any(p.requires_grad for p in self.backbone.parameters()):
-                raise NotImplementedError("training the 2D stage with a trainable backbone is not built: the trunk's backward is missing; freeze "
-                                          "the backbone's parameters (the reference's SOLVER.FIX_BACKBONE; the shipped disparity / 3D "
-                                          "configs freeze the whole stage)")
+            train_fpn = any(p.requires_grad for p in self.backbone.parameters())
+            if train_fpn and (self.backbone.body.training or any(p.requires_grad for p in self.backbone.body.parameters())):
+                raise NotImplementedError("training the 2D stage with a trainable ResNet body is not built: of the trunk's backward the FPN's "
+                                          "half exists, the body's batch-statistics BatchNorm and its backward are missing; train the FPN "
+                                          "behind a frozen body (backbone.freeze_body()) or freeze the backbone's parameters (the reference's "
+                                          "SOLVER.FIX_BACKBONE; the shipped disparity / 3D configs freeze the whole stage)")
             if lrtargets is None:
                 raise ValueError("In training mode, targets should be passed")
-            return self._forward_train(lrimages, lrtargets, draws)
+            return self._forward_train(lrimages, lrtargets, draws, train_fpn)
         left_images, right_images = to_image_list(lrimages["left"]), to_image_list(lrimages["right"])
         # the split-f16 layers of the trunk and of the RPN head report to ONE range guard, read once at the end of the stage; an overflow
         # (|v| > 65504: the fp32 reference has no such limit) repeats the stage on the fp32 kernels (engine.guarded)
@@ -111,11 +115,16 @@ class DispRCNN(nn.Module):
         finally:
             self.backbone.train(was_training)
 
-    def _forward_train(self, lrimages, lrtargets, draws):
+    def _forward_train(self, lrimages, lrtargets, draws, train_fpn=False):
         draws = draws or {}
         left_images, right_images = to_image_list(lrimages["left"]), to_image_list(lrimages["right"])
         left_targets, right_targets = lrtargets["left"], lrtargets["right"]
-        left_features, right_features, levels = self.frozen_features(left_images, right_images)
+        if train_fpn:
+            # the backbone in its training form (frozen body in eval under its own range guard, the FPN as an autograd Function): the maps
+            # require grad, the RPN's and the heads' backward deliver their gradients to them
+            left_features, right_features, levels = self._features(left_images, right_images)
+        else:
+            left_features, right_features, levels = self.frozen_features(left_images, right_images)
         left_prop, right_prop, proposal_losses = self.rpn(left_images, right_images, left_features, right_features, left_targets, right_targets,
                                                           blocked_levels=levels, draws=draws.get("rpn_sample"))
         head_draws = {k: draws[k] for k in ("sample", "dropout") if k in draws} or None

@@ -585,6 +585,23 @@ int64_t drc_act_bwd_blocked_scratch_doubles(int units, int C, int H);
 int drc_act_bwd_blocked(const float* dy, const float* y, int relu, int units, int C, int H, int W, int ph, int pw, float* dz, float* db,
                         double* scratch, int64_t scratch_doubles, void* stream);
 
+/* Training of the FPN (fpn.py:44-82): the two pieces of its backward that are not convolutions, on blocked 2D tensors
+ * float[N][CB][H+2p][W+2p][16] (one halo for both axes, as drc_bilinear_resize_blocked takes them).
+ * drc_bilinear_resize_blocked_bwd: grad_x (=|+= with accumulate) resize^T(grad_y) + subsample^T(grad_sub) on the interior of grad_x
+ *   [N][CB][IH+2px][IW+2px][16]; halo words and nothing else are left alone.  grad_y [N][CB][OH+2py][OW+2py][16] is the gradient of
+ *   drc_bilinear_resize_blocked's output with align_corners = 0 and OH >= IH, OW >= IW (anything else: -2); gather form, the forward's own
+ *   fp32 index and weight arithmetic, terms added in ascending (oy, ox) order -- no atomics, the same bits run to run.  grad_sub (optional)
+ *   [N][CB][(IH-1)/2+1+2ps][(IW-1)/2+1+2ps][16] is added at the even positions (2y, 2x): the adjoint of max_pool2d(1, 2, 0).  grad_y may
+ *   be NULL when grad_sub is given (OH, OW, py are then ignored).
+ * drc_channel_sums_blocked: sums[ceil(C/16)*16] = per-channel sums over all units and interior pixels (entries past C sum the padding
+ *   lanes), fp64 in a fixed order: per-block partials in `scratch` (drc_channel_sums_blocked_scratch_doubles(units, C, H) doubles), added
+ *   in block order by a second launch.  The bias gradient of a convolution with no activation behind it. */
+int drc_bilinear_resize_blocked_bwd(const float* grad_y, float* grad_x, int N, int CB, int IH, int IW, int px, int OH, int OW, int py,
+                                    int align_corners, int accumulate, const float* grad_sub, int ps, void* stream);
+int64_t drc_channel_sums_blocked_scratch_doubles(int units, int C, int H);
+int drc_channel_sums_blocked(const float* x, int units, int C, int H, int W, int ph, int pw, float* sums, double* scratch,
+                             int64_t scratch_doubles, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * a10. PSMLoss / EndPointErrorLoss (utils/loss_utils.py:9-32, utils/stereo_utils.py:185-208).
  *   sums5 = { sum m*smoothl1(p1-t), sum m*smoothl1(p2-t), sum m*smoothl1(p3-t), sum m, sum m*|p1-t| }   (overwritten)
