@@ -7,10 +7,11 @@ are held on the host by tests/test_srpn_train_host.py.
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from tests import srpn_train_cases as CS
 from tests import srpn_train_oracle as TO
+from tests.head_kernels_oracle import active_pixels_np as np_active       # the hand-built masks and the numpy restatements of the kernels
+from tests.head_kernels_oracle import batch_masks, col2im_np, gather_rows_np, image_a, row_coords
 from tests.helpers import golden_npz
 
 pytestmark = pytest.mark.gpu
@@ -44,77 +45,6 @@ def check(got, ref64, ref32, what, rel=2e-5):
     bound = 2 * e32 + rel * mag
     print(f"{what}: err {err:.3g} e32 {e32:.3g} bound {bound:.3g} (|ref| <= {mag:.3g})")
     assert np.isfinite(got).all() and err <= bound, what
-
-
-# ------------------------------------------------------------------------------------------------ hand-built masks
-def pix_offsets(shapes):
-    off = [0]
-    for h, w in shapes:
-        off.append(off[-1] + h * w)
-    return off
-
-
-def set_anchor(mask, shapes, A, lvl, y, x, a):
-    h, w = shapes[lvl]
-    assert 0 <= y < h and 0 <= x < w and 0 <= a < A
-    mask[(pix_offsets(shapes)[lvl] + y * w + x) * A + a] = 1
-
-
-def image_a(shapes, A, cap):
-    """a positive and a negative on one pixel, three anchors on the pixel to its right, the pixels below and diagonally below (horizontal,
-    vertical and diagonal neighbours), then the four corners of every level from the last level down while `cap` distinct pixels hold
-    them; the last level's bottom-right corner carries the LAST anchor of the last level"""
-    P = pix_offsets(shapes)[-1]
-    pos, neg = np.zeros(P * A, np.uint8), np.zeros(P * A, np.uint8)
-    set_anchor(pos, shapes, A, 0, 1, 1, 0), set_anchor(neg, shapes, A, 0, 1, 1, A - 1)
-    for a in range(A):
-        set_anchor(neg if a % 2 else pos, shapes, A, 0, 1, 2, a)
-    set_anchor(neg, shapes, A, 0, 2, 1, 1 % A), set_anchor(pos, shapes, A, 0, 2, 2, 0)
-    used = 4
-    for lvl in reversed(range(len(shapes))):
-        h, w = shapes[lvl]
-        if used + 4 > cap:
-            break
-        for k, (y, x) in enumerate(((0, 0), (0, w - 1), (h - 1, 0), (h - 1, w - 1))):
-            set_anchor(pos if k % 2 else neg, shapes, A, lvl, y, x, A - 1 if k == 3 else k % A)
-        used += 4
-    return pos, neg, used
-
-
-def image_full(shapes, A, cap):
-    """exactly `cap` anchors on `cap` distinct pixels"""
-    P = pix_offsets(shapes)[-1]
-    assert 3 * cap + 1 <= P
-    pos, neg = np.zeros(P * A, np.uint8), np.zeros(P * A, np.uint8)
-    for k in range(cap):
-        (pos if k % 3 else neg)[(3 * k + 1) * A + k % A] = 1
-    return pos, neg
-
-
-def image_none(shapes, A):
-    P = pix_offsets(shapes)[-1]
-    return np.zeros(P * A, np.uint8), np.zeros(P * A, np.uint8)
-
-
-def np_active(pos, neg, N, A, shapes, cap):
-    """the numpy restatement of drc_srpn_active_pixels"""
-    off = pix_offsets(shapes)
-    P = off[-1]
-    on = (pos.astype(bool) | neg.astype(bool)).reshape(N, P, A).any(2)
-    row_pix, counts, index = -np.ones(N * cap, np.int32), np.zeros(N, np.int32), -np.ones((N, P), np.int32)
-    for i in range(N):
-        q = np.nonzero(on[i])[0][:cap]
-        row_pix[i * cap: i * cap + len(q)], counts[i] = q, len(q)
-        index[i, q] = i * cap + np.arange(len(q))
-    flat = np.concatenate([index[:, a:b].reshape(-1) for a, b in zip(off[:-1], off[1:])])
-    return row_pix, counts, flat
-
-
-def batch_masks(which, N, shapes, A, cap):
-    """call 0: [image_a] or [image_a, none]; call 1 (other masks, the same buffers): [exactly cap] or [exactly cap, image_a]"""
-    a = image_a(shapes, A, cap)[:2]
-    imgs = ([a, image_none(shapes, A)] if which == 0 else [image_full(shapes, A, cap), a])[:N]
-    return np.concatenate([p for p, _ in imgs]), np.concatenate([n for _, n in imgs])
 
 
 # ------------------------------------------------------------------------------------------------ 1. active pixels
@@ -164,23 +94,10 @@ def test_gather_rows(C):
     _, _, G_obj_only = ST().gather_rows(row_pix, N, A, C, cap, shapes, grads=(gz, gb), g_obj=s_obj, g_box=None)
     _, _, G_box_only = ST().gather_rows(row_pix, N, A, C, cap, shapes, grads=(gz, gb), g_obj=None, g_box=s_box)
     R = N * cap
-    wT, wX, wG = torch.zeros(R, 4 * C), torch.zeros(2 * R, 9 * C), torch.zeros(R, 8 * A)
-    off = pix_offsets(shapes)
-    ul = [F.unfold(f.cpu(), 3, padding=1) for f in fl]       # [N, C*9, H*W], (c, ky, kx) rows, zeros outside the map: pure copies
-    ur = [F.unfold(f.cpu(), 3, padding=1) for f in fr]
-    edge = 0
-    for r in range(R):
-        q, img = int(rp[r]), r // cap
-        if q < 0:
-            continue
-        l = max(k for k in range(len(shapes)) if q >= off[k])
-        (h, w), p = shapes[l], q - off[l]
-        y, x = divmod(p, w)
-        edge += y in (0, h - 1) or x in (0, w - 1)
-        wT[r] = hid_dense[l][img, :, y, x].cpu()
-        wX[r], wX[R + r] = ul[l][img, :, p], ur[l][img, :, p]
-        wG[r, :2 * A] = (gz[l][img, :, y, x] * s_obj).cpu()
-        wG[r, 2 * A:] = (gb[l][img, :, y, x] * s_box).cpu()
+    wT, wX, wG = gather_rows_np(rp, N, A, C, cap, shapes, hidden=[host(d) for d in hid_dense], feats=([host(f) for f in fl], [host(f) for f in fr]),
+                                grads=([host(g) for g in gz], [host(g) for g in gb]), s_obj=host(s_obj)[0], s_box=host(s_box)[0])
+    wT, wX, wG = torch.from_numpy(wT), torch.from_numpy(wX), torch.from_numpy(wG)
+    edge = sum(y in (0, shapes[l][0] - 1) or x in (0, shapes[l][1] - 1) for _, _, l, y, x, _ in row_coords(rp, shapes, cap))
     assert edge >= 20 and (rp < 0).sum() == R - 25           # corners of every level; zero rows past the counts
     assert torch.equal(T.cpu(), wT) and torch.equal(Xcol.cpu(), wX) and torch.equal(G.cpu(), wG)
     live = torch.from_numpy(rp >= 0)
@@ -203,26 +120,7 @@ def test_col2im(C):
     dl, dr = ST().col2im(dx, index, N, A, C, cap, shapes)
     dl2, dr2 = ST().col2im(dx, index, N, A, C, cap, shapes)
     only_l, none_r = ST().col2im(dx, index, N, A, C, cap, shapes, want_right=False)
-    off = pix_offsets(shapes)
-    for dtype in (np.float64, np.float32):
-        ref = [[np.zeros((N, C, h, w), dtype) for h, w in shapes] for _ in range(2)]
-        for tap in range(9):                                 # the kernel's order: taps (ky, kx) ascending, one addition each
-            ky, kx = divmod(tap, 3)
-            for r in range(R):
-                q, img = int(rp[r]), r // cap
-                if q < 0:
-                    continue
-                l = max(k for k in range(len(shapes)) if q >= off[k])
-                (h, w), p = shapes[l], q - off[l]
-                y, x = divmod(p, w)
-                yy, xx = y + ky - 1, x + kx - 1
-                if 0 <= yy < h and 0 <= xx < w:
-                    for view in range(2):
-                        ref[view][l][img, :, yy, xx] += dxcol[view * R + r].numpy().reshape(C, 9)[:, tap].astype(dtype)
-        if dtype is np.float64:
-            ref64 = ref
-        else:
-            ref32 = ref
+    ref64, ref32 = (col2im_np(dxcol.numpy(), rp, N, C, cap, shapes, dtype) for dtype in (np.float64, np.float32))
     active_levels = set()
     for view, got in enumerate((dl, dr)):
         for l in range(len(shapes)):
