@@ -30,6 +30,7 @@ class _Site:
         self.w = E.pack_conv_weight(w)
         self.w16 = E.pack_weight_t16(w) if tuple(w.shape[2:]) == (3, 3) else None      # 3x3 layers: LDS-free kernel's packing
         self._weight, self._ww, self._s16 = w, None, None
+        self.conv, self.bn = conv, bn                                                   # the training form reads the modules (body_train.py)
         cp = E.cout_pad_of(w.shape[0])
         if bn is not None:
             self.scale, self.shift = E.fold_bn(bn.weight.detach().to(device).float(), bn.bias.detach().to(device).float(),
@@ -324,7 +325,18 @@ class BackboneRuntime:
                            enabled=bool(getattr(self.model, "overflow_check", True)))
         return fpn_train.run(self, self.model.fpn, ws, x.shape[0], [None] * 4)      # (a module: the package does not re-export its function)
 
+    def forward_body_train(self, x):
+        """The training form with a trainable body (backbone.enable_body_training()): batch-statistics BatchNorm at every site whose module is
+        in training mode, the frozen prefix under no_grad, ONE autograd Function over the trainable stages (body_train.py) and the FPN's
+        Function behind its C maps.  fp32 plans only: no split-f16 bridge and no range guard, as in every training form here."""
+        from . import body_train
+        E.require_gpu(x, "backbone input")
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"expected [N,3,H,W], got {tuple(x.shape)}")
+        return body_train.forward_body(self, x)
+
     def _forward_once(self, x, body_only=False):
+        self._pass = getattr(self, "_pass", 0) + 1      # a forward overwrites the workspace: body_train's backward checks this count
         N, _, H, W_ = x.shape
         Wt = self._compile()
         ws = self._workspace(N, H, W_)

@@ -13,8 +13,9 @@ runs in its eval form under no_grad (its range guard around the backbone only), 
 features: forward(lrimages, lrtargets) returns the merged loss dict (loss_classifier, loss_box_reg, loss_mask, loss_objectness,
 loss_rpn_box_reg).  A sub-module in eval mode contributes no losses (the reference's FIX_RPN / FIX_BOX_HEAD).  With only backbone.fpn.*
 trainable and the body in eval (backbone.freeze_body()) the backbone runs in its training form instead -- frozen body under no_grad, the
-FPN as an autograd Function (backbone/fpn_train.py) -- and the five losses reach the FPN's parameters.  What is still missing for
-training the whole 2D stage: the ResNet body's backward (batch-statistics BatchNorm, bottleneck backward) only."""
+FPN as an autograd Function (backbone/fpn_train.py) -- and the five losses reach the FPN's parameters.  After the opt-in
+backbone.enable_body_training(freeze_at) the body trains as well (backbone/body_train.py: batch-statistics BatchNorm, bottleneck
+backward); without it a trainable body is refused as before.  Still missing: the stem (freeze_at = 0)."""
 from types import SimpleNamespace
 
 import torch
@@ -64,7 +65,10 @@ class DispRCNN(nn.Module):
         (StereoRPN.forward, ROIBoxHead), so that a step can be repeated."""
         if self.training:
             train_fpn = any(p.requires_grad for p in self.backbone.parameters())
-            if train_fpn and (self.backbone.body.training or any(p.requires_grad for p in self.backbone.body.parameters())):
+            # (an opted-in backbone -- enable_body_training() -- trains its body too: the same branch, the maps require grad)
+            train_body = getattr(self.backbone, "_body_training", False)
+            train_fpn = train_fpn or train_body
+            if train_fpn and not train_body and (self.backbone.body.training or any(p.requires_grad for p in self.backbone.body.parameters())):
                 raise NotImplementedError("training the 2D stage with a trainable ResNet body is not built: of the trunk's backward the FPN's "
                                           "half exists, the body's batch-statistics BatchNorm and its backward are missing; train the FPN "
                                           "behind a frozen body (backbone.freeze_body()) or freeze the backbone's parameters (the reference's "

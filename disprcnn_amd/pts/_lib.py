@@ -89,6 +89,9 @@ _SIGS = {
     "drc_det2d_srpn_loss_fwd": (_I, [_I, _I, _I, _P, _L, _P, _P, _P, _P, _D, _P, _P, _P]),
     "drc_det2d_fastrcnn_loss_fwd": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "drc_det2d_mask_loss_fwd": (_I, [_I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "drc_conv1x1_wgrad_default_chunk": (_I, []),
+    "drc_conv1x1_wgrad_scratch_floats": (_L, [_I, _I, _I, _I, _I, _I]),
+    "drc_conv1x1_wgrad_blocked": (_I, [_P, _L, _L, _L, _L, _P, _L, _L, _L, _L, _I, _I, _I, _I, _I, _I, _I, _P, _P, _L, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

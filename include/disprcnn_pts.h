@@ -472,6 +472,24 @@ int drc_det2d_mask_loss_fwd(int N, const int32_t* roi_off, const int32_t* inst_o
                             const int64_t* table, int32_t* count, uint8_t* targets, float* grad_logits, double* partials, float* terms,
                             void* stream);
 
+/* -------------------------------------------------------------------------------------
+ * ResNet body training (body_train.hip): the weight gradient of a 1x1 convolution as a GEMM over pixels.
+ *
+ * drc_conv1x1_wgrad_blocked -- gw[co][ci] = sum_{n,y,x} b[n,co,y,x] * a[n,ci,s*y,s*x], s = stride in {1, 2}.  a and b are blocked fp32
+ *   tensors float[N][CB][H+2ph][W+2pw][16] of any halo, each given as its strides in floats (unit, channel block, row) and the offset of
+ *   its interior's first element inside a (unit, channel block); b's interior is OH x OW, a's must reach (s*(OH-1), s*(OW-1)).  cin / cout
+ *   are the UNPADDED channel counts: gw is dense fp32 [cout][cin], every element overwritten, and the padded channels of a last block do
+ *   not reach it.  The flat pixel index is cut into chunks of `chunk` pixels (> 0): fp32 (v_mfma_f32_16x16x4_f32) within a chunk,
+ *   partials [chunks][cout][cin] to scratch, a finishing launch adds them in chunk order in fp64 and rounds once.  No atomics; the bits
+ *   depend on the operands and on `chunk` only.  N = 0: zeros.  scratch_floats < drc_conv1x1_wgrad_scratch_floats(...): -3.
+ * ------------------------------------------------------------------------------------- */
+int drc_conv1x1_wgrad_default_chunk(void);
+int64_t drc_conv1x1_wgrad_scratch_floats(int N, int OH, int OW, int cin, int cout, int chunk);
+int drc_conv1x1_wgrad_blocked(const float* a, int64_t a_n_stride, int64_t a_cb_stride, int64_t a_h_stride, int64_t a_off0,
+                              const float* b, int64_t b_n_stride, int64_t b_cb_stride, int64_t b_h_stride, int64_t b_off0,
+                              int N, int OH, int OW, int cin, int cout, int stride, int chunk, float* gw, float* scratch,
+                              int64_t scratch_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
