@@ -92,6 +92,10 @@ _SIGS = {
     "drc_conv1x1_wgrad_default_chunk": (_I, []),
     "drc_conv1x1_wgrad_scratch_floats": (_L, [_I, _I, _I, _I, _I, _I]),
     "drc_conv1x1_wgrad_blocked": (_I, [_P, _L, _L, _L, _L, _P, _L, _L, _L, _L, _I, _I, _I, _I, _I, _I, _I, _P, _P, _L, _P]),
+    "drc_input_default_max_blocks": (_I, []),
+    "drc_input_batch_fwd": (_I, [_P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "drc_mask_job_cols": (_I, []),
+    "drc_mask_resize_flip_fwd": (_I, [_P, _I, _L, _I, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -14,9 +14,9 @@ from ..csrc.build import FLAGS, HIPCC
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["points.hip", "pointnet2.hip", "boxes3d.hip", "pn2_mlp.hip", "rcnn_ops.hip", "frame_ops.hip", "kitti_eval.hip",
            "train_targets.hip", "pn2_mlp_bwd.hip", "proposal_target.hip", "solver.hip", "pn2_bn.hip", "match2d.hip", "frame_ops_train.hip",
-           "det_train.hip", "body_train.hip"]
+           "det_train.hip", "body_train.hip", "input_ops.hip"]
 HEADER = os.path.join(HERE, "..", "..", "include", "disprcnn_pts.h")
-SHARED = [os.path.join(HERE, h) for h in ("box3d_pt.h", "box3d_iou.h", "mask_resize.h")]     # included by boxes3d.hip, rcnn_ops.hip, proposal_target.hip; det_train.hip
+SHARED = [os.path.join(HERE, h) for h in ("box3d_pt.h", "box3d_iou.h", "mask_resize.h")]     # included by boxes3d.hip, rcnn_ops.hip, proposal_target.hip; det_train.hip, input_ops.hip
 LIB = os.path.join(HERE, "libdisprcnn_pts.so")
 MAX_JOBS = 16
 

@@ -6,9 +6,29 @@ utils/kitti_utils.py:Calibration).
 ty`, float64 as NumPy computes them) and forwards any other attribute to the wrapped object.  `img_to_rect` / `depthmap_to_rect` on
 torch tensors have the reference's arithmetic: fp32 tensors with the intrinsics as scalars, points in the x-major order of
 meshgrid(x, y).
+
+`resize` / `crop` return a new Calib whose projection matrices follow the image (reference :48-76), so a target that went through
+`BoxList.resize` carries the intrinsics of the image it now describes.
 """
+import warnings
+
 import numpy as np
 import torch
+
+_MATRICES = ("P0", "P2", "P3")
+
+
+class _Replaced:
+    """A calibration source with some projection matrices replaced; every other attribute comes from the original."""
+
+    def __init__(self, source, matrices):
+        self._source = source
+        self.__dict__.update(matrices)
+
+    def __getattr__(self, name):
+        if name.startswith("__") or name == "_source":
+            raise AttributeError(name)
+        return getattr(self._source, name)
 
 
 class CameraIntrinsics:
@@ -20,9 +40,23 @@ class CameraIntrinsics:
         self.P3 = np.asarray(source.P3, dtype=np.float64).reshape(3, 4)
 
     def __getattr__(self, name):
-        if name == "source":
+        if name == "source" or name.startswith("__"):   # no special method is borrowed from the source: copy / pickle see this class
             raise AttributeError(name)
         return getattr(self.source, name)
+
+    def stored_matrices(self):
+        """{name: [3,4] array} of the projection matrices the source has among P0 / P2 / P3: copies, in the floating dtype the source
+        stores them in (the reference divides its float32 matrices in float32), float64 for anything that is not floating."""
+        out = {}
+        for name in _MATRICES:
+            if name in ("P2", "P3") or hasattr(self.source, name):
+                m = np.array(getattr(self.source, name)).reshape(3, 4)
+                out[name] = m if np.issubdtype(m.dtype, np.floating) else m.astype(np.float64)
+        return out
+
+    def replaced(self, matrices):
+        """-> a copy of these intrinsics over the same source with `matrices` ({name: [3,4]}) in place of its own."""
+        return CameraIntrinsics(_Replaced(self.source, matrices))
 
     @property
     def cu(self):
@@ -116,6 +150,33 @@ class Calib:
 
     def transpose(self, method):
         return self
+
+    def resize(self, dst_size):
+        """dst_size = (width, height) -> the calibration of the resampled image: row 0 of P0 / P2 / P3 / width * new width, row 1
+        / height * new height, in that order and in the dtype the matrices are stored in (reference :59-76).  A negative size returns
+        self with a warning, like the reference."""
+        if len(dst_size) != 2:
+            raise ValueError("dst_size is (width, height)")
+        if any(a < 0 for a in dst_size):
+            warnings.warn("dst size < 0, size will not change")
+            return self
+        width, height = dst_size
+        mats = self.calib.stored_matrices()
+        for m in mats.values():
+            m[0] = m[0] / self.width * width
+            m[1] = m[1] / self.height * height
+        return Calib(self.calib.replaced(mats), (width, height))
+
+    def crop(self, box):
+        """box = (x1, y1, x2, y2) -> the calibration of the window: the principal point of P0 / P2 / P3 moves by (-x1, -y1), the size is
+        the window's.  This is what reference :48-57 spells out; there the six assignments land on tensors that its P0 / P2 / P3
+        properties build afresh, so only the size changes.  The shift is applied here."""
+        x1, y1, x2, y2 = (v.item() if torch.is_tensor(v) else v for v in box)
+        mats = self.calib.stored_matrices()
+        for m in mats.values():
+            m[0, 2] = m[0, 2] - x1
+            m[1, 2] = m[1, 2] - y1
+        return Calib(self.calib.replaced(mats), (x2 - x1, y2 - y1))
 
     def img_to_rect(self, u, v, depth_rect):
         """Image coordinates + depth -> rectified camera coordinates [N,3]."""

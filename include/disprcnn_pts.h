@@ -490,6 +490,30 @@ int drc_conv1x1_wgrad_blocked(const float* a, int64_t a_n_stride, int64_t a_cb_s
                               int N, int OH, int OW, int cin, int cout, int stride, int chunk, float* gw, float* scratch,
                               int64_t scratch_floats, void* stream);
 
+/* -------------------------------------------------------------------------------------
+ * Input pipeline (input_ops.hip): decoded uint8 images -> the padded fp32 batch of an ImageList; resize / flip of instance masks.
+ *
+ * drc_input_batch_fwd -- out fp32 [I,3,Hp,Wp]: out[i][c][y][x] = lut[c][ src_i[ytab_i[y]][xtab_i[x]][chan_c] ] for y < out_h_i and
+ *   x < out_w_i, +0.0 elsewhere.  Every element, padding included, is written exactly once (no memset; `out` may be uninitialised and
+ *   needs 4-byte alignment only: whole quads are 16-byte stores, the clipped first / last quad goes element by element).
+ *   src: packed uint8 HWC RGB images, src_bytes long.  tables: int32, table_ints long: I descriptors of 8 ints (src_off into src, src_h,
+ *   src_w, out_h, out_w, ytab_off, xtab_off into tables, 0) followed by the index tables (out_h + out_w entries per image; they carry
+ *   the resize and the flip).  lut: fp32 [3][256].  chan0..2: the source channel of each output channel, in 0..2.  Table positions,
+ *   table entries and byte indices are clamped into their buffers.  The grid is min(quads / 256, max_blocks) workgroups that stride;
+ *   drc_input_default_max_blocks() is what the callers pass.  I = 0 or an empty plane: nothing is launched.  Hp * Wp >= 2^31: -2.
+ *
+ * drc_mask_resize_flip_fwd -- n_jobs jobs of drc_mask_job_cols() int64 each, on the device: src pointer (uint8 [G,H,W], 0/1), dst pointer
+ *   (uint8 [G,oh,ow]), G, H, W, oh, ow, flip, first quad, quads (= ceil(G*oh*ow / 4)); first quads ascend from 0 and sum to `quads`; jobs
+ *   without output are left out by the caller.  Taps and weights of mask_resize.h:resize_axis; a pixel is 1 iff every tap whose fp32
+ *   weight is non-zero is 1 (the truncated bilinear blend in exact arithmetic; no floating-point sum).  flip: column x reads the resized
+ *   column ow-1-x.  Equal sizes copy (or flip) exactly.  n_jobs = 0 or quads = 0: nothing is launched.
+ * ------------------------------------------------------------------------------------- */
+int drc_input_default_max_blocks(void);
+int drc_input_batch_fwd(const uint8_t* src, int64_t src_bytes, const int32_t* tables, int64_t table_ints, const float* lut, int chan0,
+                        int chan1, int chan2, int I, int Hp, int Wp, float* out, int max_blocks, void* stream);
+int drc_mask_job_cols(void);
+int drc_mask_resize_flip_fwd(const int64_t* jobs, int n_jobs, int64_t quads, int max_blocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
